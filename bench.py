@@ -2,7 +2,15 @@
 """Benchmark: images/sec for one full KFAC factor pass + factor inversion (MNIST MLP).
 
     python bench.py [--gpus N --steps K --warmup W] [--config mlp|lenet|wide]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: it sets up, settles the
+GPU's clocks on the workload, warms up, times the K steps, writes the last timed
+step's factors and L factors to `DIR/<name>.npy` if `--dump-outputs DIR` is given
+(dump_outputs), and prints the result line.  Everything under "Also reported" below,
+the other configs, the eigenvalue leg, the serial figure and the N > 1 verification
+pass run only with `--full`; their fields are null in a plain run's line.
 
 `--gpus N > 1` without a launcher's WORLD_SIZE: this process spawns the N rank
 processes itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / a free
@@ -30,7 +38,7 @@ inversion k overlaps pass k+1.  `serial_images_per_s` is the reference scripts' 
 (classification_ll_block.py:93-106: a pass, then invert, its result read before the
 next pass) = images / (T_pass + T_invert).
 
-Also reported (same JSON line): the roofline of the dominant kernel
+Also reported (same JSON line, `--full` only): the roofline of the dominant kernel
 (kfac_factor_tiles, fp32 MFMA, or kfac_factor_syrk3, bf16x3 MFMA, for the wide
 config's n >= 2048 factors; HIP-event durations measured live on its stream),
 the pass/all-reduce/invert split, the serial rate (one pass, then invert on the
@@ -63,6 +71,7 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0
 SYRK3_PEAK_TFLOPS = MFMA_BF16_PEAK_TFLOPS / 6
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E (MI355X_MICROARCH.md)
 DAMPING = (0.2 ** 2, 200)     # invert(std**2, N), classification_ll_block.py:72-73,106
+SETTLE_S = 1.0  # a plain run's untimed passes before its warmup (the GPU's clock ramp)
 
 
 class Layer:
@@ -525,6 +534,30 @@ def eig_cpu_baseline(sizes=EIG_SIZES, threads=None, budget_s=6.0):
                                       f"fp32 factor, fp32 as the reference's symeig, per size"}
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # --dump-outputs: all arrays together (64 MB with headers to spare)
+
+
+def dump_outputs(path, kfac, layers):
+    """Write what the caller of the timed path holds after its last step, as float32
+    `<path>/layer<i>_{A,G,L_A,L_G}.npy`: every layer's factors (kfac.state) and their L
+    factors (kfac.inv_state, verdicts settled).  An array whose share of the byte budget
+    (DUMP_BUDGET_BYTES / number of arrays) it exceeds is written as a fixed sample of
+    its flattened elements instead (sorted indices drawn with seed 0 from its size, so
+    two builds write the same elements): C5's 4097^2 factors."""
+    inv = kfac.inv_state
+    arrays = {}
+    for i, layer in enumerate(layers):
+        for name, t in zip(("A", "G", "L_A", "L_G"), list(kfac.state[layer]) + list(inv[layer])):
+            arrays[f"layer{i}_{name}"] = t
+    cap = DUMP_BUDGET_BYTES // (4 * len(arrays))  # elements per array
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 # ------------------------------------------------------------------ launcher
 def _free_port():
     with socket.socket() as s:
@@ -592,6 +625,15 @@ def main(argv=None):
     ap.add_argument("--images", type=int, default=None, help="images per rank per pass")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: 65,536 x 64 images in global batches of 65,536 over the N ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the other configs, the eigensolver leg, "
+                         "the serial and end-to-end figures, the instrumented repetition (roofline, "
+                         "breakdown), the CPU baselines and, N > 1, the verification pass (the --no-* "
+                         "options below drop single legs of a --full run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's factors and L factors to "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of an array over its share of "
+                         "64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--no-serial", action="store_true")
@@ -656,7 +698,7 @@ def main(argv=None):
     from bnn_kfac_amd.distributed import DistributedKFAC
 
     others = None
-    if world == 1 and args.config == "mlp" and not args.no_other_configs and not args.strong:
+    if args.full and world == 1 and args.config == "mlp" and not args.no_other_configs and not args.strong:
         # BASELINE's other single-GPU configs (C5 wide MLP, C3 LeNet-5), GPU-only, in
         # the same run, BEFORE the headline: from an idle GPU the pipelined MLP step
         # takes ~60 steps to settle (0.38 -> 0.34 ms per step in blocks of 20,
@@ -666,7 +708,7 @@ def main(argv=None):
                   "C3": other_config("lenet", device, steps=20, warmup=2)}
         torch.cuda.empty_cache()
     eig = None
-    if world == 1 and args.config == "mlp" and not args.no_eig and not args.strong:
+    if args.full and world == 1 and args.config == "mlp" and not args.no_eig and not args.strong:
         eig = eig_leg(device)
 
     specs = CONFIGS[args.config]
@@ -750,7 +792,7 @@ def main(argv=None):
     # the headline's SYRK (312 vs 295 us per launch, 1.61e8 vs 1.73e8 img/s on one box,
     # profiles/r05p/).
     serial = None
-    if not args.no_serial:
+    if args.full and not args.no_serial:
         # the caller who runs a pass, inverts on its own stream and reads the result
         # before the next pass (classification_ll_block.py:93-106): no overlap
         kfac.overlap_invert = False
@@ -768,6 +810,15 @@ def main(argv=None):
         kfac.overlap_invert = True
         kfac.launch_first = pipe_launch_first
 
+    if not args.full:
+        # a plain run has none of those legs in front of the headline: part of its set-up
+        # is SETTLE_S seconds of the pipelined pass itself, so that the warmup and the
+        # timed steps find the GPU past the same clock ramp
+        t1 = time.perf_counter()
+        while max_over_ranks(time.perf_counter() - t1) < SETTLE_S:  # every rank: as many passes
+            one_pass()
+        kfac.inv_state
+        sync()
 
     for _ in range(args.warmup):
         one_pass()
@@ -782,6 +833,11 @@ def main(argv=None):
     kfac.inv_state
     sync()
     elapsed = max_over_ranks(time.perf_counter() - t0)
+
+    if args.dump_outputs and rank == 0:
+        # before any later leg runs the pass again: the last TIMED step's results
+        # (N > 1: the all-reduced factors, the same on every rank)
+        dump_outputs(args.dump_outputs, kfac, layers)
 
     if args.host_profile:
         import cProfile
@@ -812,20 +868,20 @@ def main(argv=None):
     # Kernel durations: the same K steps again with the library's HIP-event timing
     # on (events recorded around each launch, on its stream).  Kept out of the timed
     # region above because the event packets add ~10 us per launch boundary.
-    comm["timing"] = True
-    if world > 1:  # the side-stream collective (DistributedKFAC.side_collective) times itself
-        kfac.comm_events = comm.setdefault("events", [])
-    prof = profiled_steps(N, one_pass, kfac, sync, args.steps)
-    comm["timing"] = False
-    if world > 1:
-        kfac.comm_events = None
-    allreduce_ms = None
-    if world > 1:
-        allreduce_ms = max_over_ranks(sum(a.elapsed_time(b) for a, b in comm.pop("events", []))
-                                      / args.steps)
+    prof = allreduce_ms = None
+    if args.full:
+        comm["timing"] = True
+        if world > 1:  # the side-stream collective (DistributedKFAC.side_collective) times itself
+            kfac.comm_events = comm.setdefault("events", [])
+        prof = profiled_steps(N, one_pass, kfac, sync, args.steps)
+        comm["timing"] = False
+        if world > 1:
+            kfac.comm_events = None
+            allreduce_ms = max_over_ranks(sum(a.elapsed_time(b) for a, b in comm.pop("events", []))
+                                          / args.steps)
 
     e2e = None
-    if not args.no_e2e and world == 1:
+    if args.full and not args.no_e2e and world == 1:
         x = torch.rand(images, *specs[0].in_shape, device=device)
         crit = torch.nn.CrossEntropyLoss()
 
@@ -856,19 +912,19 @@ def main(argv=None):
     images_total = world * images * args.steps
     value = images_total / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
-    roofline, breakdown = roofline_of(prof, specs, images, args.steps, args.config)
+    roofline, breakdown = None, {}
+    if prof is not None:
+        roofline, breakdown = roofline_of(prof, specs, images, args.steps, args.config)
     breakdown.update({"allreduce_ms_per_step": allreduce_ms,
                       "host_issue_ms_per_step": 1e3 * t_issue / args.steps,
                       "updates_per_step": len(starts)})
 
-
     parity = None
-    if world > 1 and not args.no_parity:
+    if args.full and world > 1 and not args.no_parity:
         parity = verify_parity(kfac, net, specs, recs, batch, images, world, rank, device, sync)
 
-
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the host's best: every thread count this process may use -- its CPU affinity,
         # its cgroup CPU quota and OMP_NUM_THREADS (the box's per-GPU share) -- timed,
         # the fastest reported (`cores` = its thread count), and 1 thread beside them
@@ -908,6 +964,7 @@ def main(argv=None):
         out = {"metric": METRIC, "value": value, "unit": "images/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
                "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
+               "full": args.full,
                "vs_baseline": None, "dtype": "f32",
                "metric_variant": ("pipelined: inversion k overlaps pass k+1 (eager_verdict=False); "
                                   "serial_images_per_s = images / (T_pass + T_invert), the "

@@ -14,7 +14,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 # the pipelined loop only (its launches are the roofline line's); no eig leg (a
 # cooperative launch + --pmc finalisation crash the profiler's exit)
-BENCH="python3 bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-serial --no-other-configs --no-eig"
+BENCH="python3 bench.py --config $CFG --full --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-serial --no-other-configs --no-eig"
 ok() { [ "$1" -eq 0 ]; }
 
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- $BENCH > $OUT/trace.log 2>&1

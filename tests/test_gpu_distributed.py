@@ -181,9 +181,9 @@ def test_rccl_two_ranks_two_gpus(hip_device, shape, shard):
 
 
 def test_bench_two_ranks_parity_field(tmp_path):
-    """`bench.py --gpus 2` end to end on one device (--shared-device: gloo instead of
-    RCCL, both ranks on GPU 0): the JSON line carries the post-timing verification
-    pass's verdict, and it is true."""
+    """`bench.py --gpus 2 --full` end to end on one device (--shared-device: gloo instead
+    of RCCL, both ranks on GPU 0): the JSON line carries the post-timing verification
+    pass's verdict (a --full leg), and it is true."""
     import json
     import subprocess
     import sys
@@ -191,7 +191,7 @@ def test_bench_two_ranks_parity_field(tmp_path):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--shared-device",
-                          "--steps", "2", "--warmup", "1", "--no-serial", "--images", "32768"],
+                          "--full", "--steps", "2", "--warmup", "1", "--no-serial", "--images", "32768"],
                          capture_output=True, text=True, timeout=240, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

@@ -5,7 +5,7 @@ set -o pipefail
 O=gpurun_out/${TAG:?set TAG}
 mkdir -p $O
 CFG=${CFG:-mlp}
-ARGS=${ARGS:-"--steps 100 --warmup 20 --no-cpu-baseline --no-e2e --no-serial --no-other-configs --no-eig"}
+ARGS=${ARGS:-"--full --steps 100 --warmup 20 --no-cpu-baseline --no-e2e --no-serial --no-other-configs --no-eig"}
 for r in $(seq 1 ${REPS:-3}); do
   for v in $AB; do
     name=${v%%:*}; dir=${v#*:}

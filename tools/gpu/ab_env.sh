@@ -4,7 +4,7 @@ set -o pipefail
 O=gpurun_out/${TAG:?set TAG}
 mkdir -p $O
 CFG=${CFG:-lenet}
-ARGS=${ARGS:-"--steps 30 --warmup 5 --no-cpu-baseline --no-e2e --no-serial --no-other-configs --no-eig"}
+ARGS=${ARGS:-"--full --steps 30 --warmup 5 --no-cpu-baseline --no-e2e --no-serial --no-other-configs --no-eig"}
 for r in $(seq 1 ${REPS:-3}); do
   for v in $ENVS; do
     name=${v%%:*}; kv=${v#*:}

@@ -13,7 +13,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   tail -1 $O/smoke.log
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_mlp.log 2>&1 || { tail -20 $O/bench_mlp.log; exit 1; }
+  timeout -k 10 500 python bench.py --gpus 1 --full --steps 20 --warmup 5 > $O/bench_mlp.log 2>&1 || { tail -20 $O/bench_mlp.log; exit 1; }
   python tools/line_summary.py $O/bench_mlp.log
 fi
 if [ "${PROF:-0}" = 1 ]; then

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${TAG:?set TAG}
 mkdir -p $O
 KRE=${KRE:-conv_x3}
-B="python3 bench.py --config lenet --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-serial --no-eig --no-other-configs"
+B="python3 bench.py --config lenet --full --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-serial --no-eig --no-other-configs"
 i=0
 for C in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_SMEM" \
          "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_INSTS_BRANCH GRBM_GUI_ACTIVE"; do

@@ -6,7 +6,7 @@ timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method threa
 tail -2 $O/conv_tests.log
 for r in 1 2 3; do
   for x in 1 0; do
-    KFAC_CONV_X3=$x timeout -k 10 300 python bench.py --config lenet --steps 30 --warmup 5 --no-cpu-baseline --no-e2e --no-serial --no-eig > $O/lenet_x3_${x}_$r.log 2>&1 || { tail -20 $O/lenet_x3_${x}_$r.log; exit 1; }
+    KFAC_CONV_X3=$x timeout -k 10 300 python bench.py --config lenet --full --steps 30 --warmup 5 --no-cpu-baseline --no-e2e --no-serial --no-eig > $O/lenet_x3_${x}_$r.log 2>&1 || { tail -20 $O/lenet_x3_${x}_$r.log; exit 1; }
     python -c "
 import json; d=json.loads(open('$O/lenet_x3_${x}_$r.log').read().strip().splitlines()[-1]); r=d['roofline']
 print('conv_x3=$x rep $r', round(d['value']), round(d['ms_per_step'],4), r['kernel'], round(r['avg_launch_us'],1), round(r['frac'],4), json.dumps({k: (round(v['ms_per_step'],4), round(v['tflops'] or 0,1)) for k,v in d['breakdown']['factor_kernels'].items()}))" | tee -a $O/ab_lenet.log
