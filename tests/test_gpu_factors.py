@@ -42,7 +42,12 @@ def test_strided_rows_and_beta(hip_device):
     F0 = rng.standard_normal((81, 81)).astype(np.float32)
     F0 = F0 + F0.T
     F = _t(F0, hip_device)
+    N.profile_reset()
+    N.profile_enable(True)
     N.factor_update([N.factor_job(N.rowmajor_operand(xt, True), F, 0.25, 1.0)], hip_device)
+    torch.cuda.synchronize()
+    N.profile_enable(False)
+    assert N.profile_read(N.PROF_FACTOR_TILES)[1] == 1  # n = 81 < 256: the fp32 tiles kernel
     x = base[:, 5:85].astype(np.float64)
     xo = np.concatenate([x, np.ones((200, 1))], 1)
     want = F0 + 0.25 * xo.T @ xo
@@ -126,6 +131,13 @@ X3F_SPECS = [(16, 6, 14, 14, 16, (5, 5), (1, 1), (0, 0), True), (64, 6, 14, 14, 
 X3S_SPECS = [(16, 1, 28, 28, 6, (5, 5), (1, 1), (2, 2), True), (256, 1, 28, 28, 6, (5, 5), (1, 1), (2, 2), True),
              (5, 2, 11, 13, 4, (3, 4), (2, 1), (1, 2), True),
              (3, 3, 12, 16, 5, (3, 3), (1, 1), (0, 1), False), (2, 2, 9, 9, 3, (4, 4), (1, 1), (1, 1), False)]
+# the A factor on kfac_factor_conv_x3 (32 < n <= 192 from an LDS im2col)
+CX3_SPECS = [(4, 2, 32, 32, 6, (5, 5), (1, 1), (2, 2), True), (5, 4, 15, 15, 8, (3, 3), (2, 2), (1, 1), False),
+             (3, 1, 20, 20, 4, (4, 8), (1, 1), (0, 0), True), (2, 20, 10, 10, 5, (3, 3), (1, 1), (0, 0), True)]
+# the A factor on the fp32 staged kernel kfac_factor_conv: n = 10, n = 224, an odd group
+# count and column stride 3 (both off kfac_factor_conv_x3s)
+CONV_SPECS = [(4, 1, 10, 10, 20, (3, 3), (1, 1), (1, 1), True), (2, 14, 9, 9, 6, (4, 4), (1, 1), (0, 0), False),
+              (2, 2, 5, 5, 3, (3, 3), (1, 1), (0, 0), True), (3, 3, 12, 17, 5, (3, 3), (1, 3), (0, 1), False)]
 
 
 @pytest.mark.parametrize("spec", [
@@ -192,6 +204,10 @@ def test_conv_shapes_vs_oracle(hip_device, spec):
         assert N.profile_read(N.PROF_FACTOR_CONV_X3S)[1] == 1
     if spec in X3F_SPECS:  # on the flattened column-copy kernel
         assert N.profile_read(N.PROF_FACTOR_CONV_X3F)[1] == 1
+    if spec in CX3_SPECS:
+        assert N.profile_read(N.PROF_FACTOR_CONV_X3)[1] == 1
+    if spec in CONV_SPECS:
+        assert N.profile_read(N.PROF_FACTOR_CONV)[1] == 1
     A, G = kfac.state[conv]
     np.testing.assert_allclose(A.cpu().numpy(), O.conv_factor_A(x, k, p, s, bias, np.float64), **FT)
     np.testing.assert_allclose(G.cpu().numpy(), O.grad_factor(gr, np.float64), **FT)
@@ -615,6 +631,13 @@ def test_deferred_reduce_matches_immediate(hip_device, model):
     for other in outs[1:]:
         for got, want in zip(other, outs[0]):
             np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6 * np.abs(want).max())
+# the A factor on kfac_factor_conv_x3 (32 < n <= 192 from an LDS im2col)
+CX3_SPECS = [(4, 2, 32, 32, 6, (5, 5), (1, 1), (2, 2), True), (5, 4, 15, 15, 8, (3, 3), (2, 2), (1, 1), False),
+             (3, 1, 20, 20, 4, (4, 8), (1, 1), (0, 0), True), (2, 20, 10, 10, 5, (3, 3), (1, 1), (0, 0), True)]
+# the A factor on the fp32 staged kernel kfac_factor_conv: n = 10, n = 224, an odd group
+# count and column stride 3 (both off kfac_factor_conv_x3s)
+CONV_SPECS = [(4, 1, 10, 10, 20, (3, 3), (1, 1), (1, 1), True), (2, 14, 9, 9, 6, (4, 4), (1, 1), (0, 0), False),
+              (2, 2, 5, 5, 3, (3, 3), (1, 1), (0, 0), True), (3, 3, 12, 17, 5, (3, 3), (1, 3), (0, 1), False)]
 
 
 @pytest.mark.parametrize("spec", [

@@ -17,6 +17,9 @@ from oracle import kfac_oracle as O
 pytestmark = pytest.mark.gpu
 
 
+SYRK3_LAUNCHES = []  # kfac_factor_syrk3 launches of wide_layer's update
+
+
 @pytest.fixture(scope="module")
 def wide_layer(hip_device):
     """One update of a Linear(4096, 4096) layer over 1024 rows (U[0,1) inputs, N(0,1)
@@ -29,7 +32,13 @@ def wide_layer(hip_device):
     a = rng.random((1024, 4096), dtype=np.float32)
     g = rng.standard_normal((1024, 4096), dtype=np.float32)
     kfac.record[net[0]] = [torch.from_numpy(a).to(hip_device), torch.from_numpy(g).to(hip_device)]
+    from bnn_kfac_amd import _native as N
+    N.profile_reset()
+    N.profile_enable(True)
     kfac.update(batch_size=1024)
+    torch.cuda.synchronize()
+    N.profile_enable(False)
+    SYRK3_LAUNCHES.append(N.profile_read(N.PROF_FACTOR_SYRK3)[1])
     A, G = (t.cpu().numpy() for t in kfac.state[net[0]])
     wantA = O.linear_factor_A(a, True, np.float64)
     wantG = O.grad_factor(g, np.float64)
@@ -39,6 +48,7 @@ def wide_layer(hip_device):
 def test_wide_syrk_vs_fp64(wide_layer):
     _, _, A, G, wantA, wantG = wide_layer
     assert A.shape == (4097, 4097) and G.shape == (4096, 4096)
+    assert SYRK3_LAUNCHES == [1]  # both factors in one launch of the split-once bf16x3 SYRK
     for got, want in ((A, wantA), (G, wantG)):
         np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-5 * np.abs(want).max())
         assert np.array_equal(got, got.T)  # written exactly symmetric
