@@ -66,6 +66,12 @@ class QuadJob(ctypes.Structure):
                 ("lower2", c_i32), ("v", c_vp)]
 
 
+class CovJob(ctypes.Structure):
+    _fields_ = [("J", c_vp), ("ldJ", c_i64), ("nA", c_i32), ("nG", c_i32), ("K1", c_vp),
+                ("ld1", c_i64), ("K2", c_vp), ("ld2", c_i64), ("lower1", c_i32),
+                ("lower2", c_i32)]
+
+
 class SampleJob(ctypes.Structure):
     _fields_ = [("LA", c_vp), ("ldA", c_i64), ("LG", c_vp), ("ldG", c_i64), ("Z", c_vp),
                 ("nA", c_i32), ("nG", c_i32), ("W", c_vp), ("ldW", c_i64), ("bias", c_vp),
@@ -118,6 +124,10 @@ SIGNATURES = {
                                                         c_i64]),
     "kfac_kron_quadform": (ctypes.c_int, [ctypes.POINTER(QuadJob), ctypes.c_int, c_i64,
                                           ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_kron_cov_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64,
+                                                        ctypes.c_int]),
+    "kfac_kron_cov": (ctypes.c_int, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                     ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "kfac_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SampleJob), ctypes.c_int]),
     "kfac_sample": (ctypes.c_int, [ctypes.POINTER(SampleJob), ctypes.c_int, ctypes.c_int, c_vp,
                                    ctypes.c_size_t, c_vp]),
@@ -429,6 +439,20 @@ def kron_quadform(jobs, nb: int, abs_sum: bool, out: torch.Tensor):
     ws = workspace.get(out.device, need)
     check(L.kfac_kron_quadform(arr, len(jobs), nb, int(abs_sum), ptr(out), ptr(ws), ws.numel(),
                                stream_handle(out.device)), "kfac_kron_quadform")
+
+
+def kron_cov_workspace_bytes(jobs, nb: int, nc: int) -> int:
+    return lib().kfac_kron_cov_workspace_bytes(as_array(CovJob, jobs), len(jobs), nb, nc)
+
+
+def kron_cov(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_kron_cov: out (nb, nc, nc) (+)= sum_j T_j T_j^T, <= 8 jobs per call."""
+    L = lib()
+    arr = as_array(CovJob, jobs)
+    need = L.kfac_kron_cov_workspace_bytes(arr, len(jobs), nb, nc)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_kron_cov(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
+                          stream_handle(out.device)), "kfac_kron_cov")
 
 
 def sample(jobs, device: torch.device, accumulate: bool) -> None:

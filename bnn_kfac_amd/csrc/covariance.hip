@@ -1,0 +1,333 @@
+// GLM predictive: the full output covariance J Sigma J^T under the KFAC posterior.
+//
+// KFAC.sample draws S = L_A z L_G^T (nA x nG), so vec(S) (index a*nG + g) has
+// covariance K1 K1^T (x) K2 K2^T with K1 = L_A, K2 = L_G.  With M_r the Jacobian row
+// r = b*nc + c (sample b, output c) viewed (nA x nG) row-major,
+//   cov[b][c][c'] = sum_layers < T_{b,c}, T_{b,c'} >_F ,   T_r = K1^T M_r K2 ,
+// never forming the Kronecker product.  Per call (<= 8 layers, nb samples, nc <= 32):
+//   apply : T_r for every row, as two GEMMs over ALL rows at once (fp32 MFMA, exact
+//           fp32 products, 64x64 tiles of contract_tile; lower-triangular K1 / K2 skip
+//           their zero K-range):
+//             U = K1^T [M_0 | M_1 | ...]   (nA x rows*nG: column j = (row j / nG, g = j % nG))
+//             T = [U_0 ; U_1 ; ...] K2     (rows*nA x nG: the U_r stacked are one tall matrix)
+//           so a layer with a narrow nG (10 classes) fills its tiles with other rows'
+//           columns instead of padding.
+//   gram  : cov_b = T_b T_b^T, K split over workgroups (each a GSEG-long segment of the
+//           nc rows, staged through LDS, narrow 32x32 MFMA), fp32 partials
+//   reduce: partials summed per sample in a fixed order (segments, then jobs) in fp64;
+//           the lower triangle is computed and mirrored, so cov[b] is bitwise symmetric.
+// Apply tasks are ordered a-tile major, heaviest first (a lower-triangular K1 leaves tile
+// a0 the K-range [a0, nA)), and run in plain block order: the round-robin dispatch gives
+// every XCD the same mix.  Contiguous per-XCD ranges (xcd_task) put the long a-tiles on
+// XCD 0 and the short ones on XCD 7 and measured 1.5x slower; K1 fits any one L2.
+#include "kfac_common.h"
+
+namespace kfac {
+
+constexpr int CMAXJ = 8;
+constexpr int CMAXC = 32;           // nc: one 32x32 MFMA quadrant
+constexpr int GSEG = 2048;          // K elements per gram workgroup (multiple of BK)
+constexpr int KFAC_ROWBATCH = 16;   // panel layout of [M_0 | M_1 | ...] (internal to this file)
+
+struct CovJobDev {
+  const float* J;
+  const float* K1;
+  const float* K2;
+  float* U;        // rows x nA*nG
+  float* T;        // rows x nA*nG, row r = K1^T M_r K2 in a*nG + g order
+  float* partial;  // nb x nseg x nc*nc
+  int64_t ldJ, ld1, ld2;
+  int nA, nG, tg, nseg, lower1, lower2;
+  int ucols, trows;                // rows*nG, rows*nA
+  int u_begin, t_begin, g_begin;   // first task in the U / T / gram launch
+};
+
+struct CovArgs {
+  int njobs, nc, accumulate;
+  int nu, nt, ng;  // tasks of the U / T / gram launch
+  int64_t nb;
+  float* cov;
+  int u_end[CMAXJ], t_end[CMAXJ], g_end[CMAXJ];
+  CovJobDev job[CMAXJ];
+};
+static_assert(sizeof(CovArgs) <= 4096, "kernel argument block");
+
+__device__ __forceinline__ int cov_find_job(const int* ends, int njobs, int task) {
+  int j = 0;
+  while (j + 1 < njobs && task >= ends[j]) ++j;
+  return j;
+}
+
+__device__ __forceinline__ OpDev rowmajor_op(const float* p, int rows, int cols, int64_t ld) {
+  OpDev d{};
+  d.ptr = p; d.layout = KFAC_ROWMAJOR; d.rows = rows; d.cols = cols; d.ld = ld; d.ones = -1;
+  return d;
+}
+
+// element (k, i) = p[i * L + k]
+__device__ __forceinline__ OpDev channel_op(const float* p, int64_t rows, int cols, int64_t L) {
+  OpDev d{};
+  d.ptr = p; d.layout = KFAC_CHANNEL; d.rows = rows; d.cols = cols; d.L = L; d.sB = 0; d.ones = -1;
+  return d;
+}
+
+// element (k, j) = p[(j / L) * sB + k * L + j % L]: row j / L of J viewed (nA x nG), L = nG
+__device__ __forceinline__ OpDev rowbatch_op(const float* p, int rows, int cols, int64_t L, int64_t sB) {
+  OpDev d{};
+  d.ptr = p; d.layout = KFAC_ROWBATCH; d.rows = rows; d.cols = cols; d.ld = L; d.L = L; d.sB = sB;
+  d.ones = -1;
+  return d;
+}
+
+// Panel<ROWMAJOR>'s thread map (16 lanes x 4 columns walk a panel row) over the columns
+// of [M_0 | M_1 | ...]: within one M_r they are contiguous, so the lanes still read whole
+// segments.  With nG, the row stride and the base multiples of 4 floats a thread's 4
+// columns lie in one M_r, 16 bytes aligned: one 16-byte load.
+template <>
+struct Panel<KFAC_ROWBATCH> {
+  static constexpr int PITCH = TILE + 4;
+  const float* base;
+  int64_t ld, kend;
+  int64_t off[4];  // offset of column c4 + q at k = 0, or -1 past the last column
+  int c4, r0;
+  bool vec;
+  __device__ __forceinline__ void init(const OpDev& op, const float* base_, int col0, int tid,
+                                       int64_t k_end, int64_t) {
+    base = base_; ld = op.ld; kend = k_end;
+    c4 = (tid & 15) * 4; r0 = tid >> 4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int j = col0 + c4 + q;
+      const int r = j / (int)op.L;
+      off[q] = j < op.cols ? r * op.sB + (j - r * (int)op.L) : -1;
+    }
+    vec = off[3] >= 0 && ((op.L & 3) == 0) && ((op.sB & 3) == 0) &&
+          ((reinterpret_cast<uintptr_t>(base) & 15) == 0);
+  }
+  __device__ __forceinline__ void load(int64_t k, float (&v)[8]) const {
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int64_t row = k + r0 + 16 * m;
+      float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (row < kend) {
+        const float* p = base + row * ld;
+        if (vec) {
+          x = *reinterpret_cast<const float4*>(p + off[0]);
+        } else {
+          float e[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) e[q] = off[q] >= 0 ? p[off[q]] : 0.f;
+          x = make_float4(e[0], e[1], e[2], e[3]);
+        }
+      }
+      v[4 * m + 0] = x.x; v[4 * m + 1] = x.y; v[4 * m + 2] = x.z; v[4 * m + 3] = x.w;
+    }
+  }
+  __device__ __forceinline__ void store(float* lds, const float (&v)[8]) const {
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+      *reinterpret_cast<float4*>(lds + (r0 + 16 * m) * PITCH + c4) =
+          make_float4(v[4 * m], v[4 * m + 1], v[4 * m + 2], v[4 * m + 3]);
+  }
+};
+
+// Apply, launch 1: one 64x64 tile of U = K1^T [M_0 | M_1 | ...]; column j = (r, g) goes
+// to U[r][a][g] (the U_r back to back: one (rows*nA x nG) matrix for launch 2).
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_apply_u(CovArgs args) {
+  __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
+  const int task = blockIdx.x;
+  const CovJobDev& C = args.job[cov_find_job(args.u_end, args.njobs, task)];
+  const int local = task - C.u_begin;
+  const int ct = (C.ucols + TILE - 1) / TILE;
+  const int a0 = (local / ct) * TILE, j0 = (local % ct) * TILE;
+  const OpDev k1 = rowmajor_op(C.K1, C.nA, C.nA, C.ld1);
+  const OpDev m = rowbatch_op(C.J, C.nA, C.ucols, C.nG, C.ldJ);
+  floatx16 acc;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+  // U[a][j] = sum_k K1[k][a] M[k][j]; K1 lower => k >= a0
+  contract_tile<KFAC_ROWMAJOR, KFAC_ROWBATCH>(k1, a0, m, j0, C.lower1 ? a0 : 0, C.nA, false, true,
+                                              lds, acc);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = j0 + (wave & 1) * 32 + (lane & 31);
+  if (j >= C.ucols) return;
+  const int r = j / C.nG, g = j - r * C.nG;
+  float* dst = C.U + (int64_t)r * C.nA * C.nG + g;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int a = a0 + (wave >> 1) * 32 + acc_row(v, lane);
+    if (a < C.nA) dst[(int64_t)a * C.nG] = acc[v];
+  }
+}
+
+// Launch 2: one 64x64 tile of T = U K2, U the (rows*nA x nG) stack
+// (A-operand element (g, i) = U[i*nG + g]).
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_apply_t(CovArgs args) {
+  __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
+  const int task = blockIdx.x;
+  const CovJobDev& C = args.job[cov_find_job(args.t_end, args.njobs, task)];
+  const int local = task - C.t_begin;
+  const int i0 = (local / C.tg) * TILE, g0 = (local % C.tg) * TILE;
+  const OpDev ut = channel_op(C.U, C.nG, C.trows, C.nG);
+  const OpDev k2 = rowmajor_op(C.K2, C.nG, C.nG, C.ld2);
+  floatx16 acc;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+  // T[i][g'] = sum_g U[i][g] K2[g][g']; K2 lower => g >= g0
+  contract_tile<KFAC_CHANNEL, KFAC_ROWMAJOR>(ut, i0, k2, g0, C.lower2 ? g0 : 0, C.nG, false, true,
+                                             lds, acc);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = g0 + (wave & 1) * 32 + (lane & 31);
+  if (g >= C.nG) return;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int i = i0 + (wave >> 1) * 32 + acc_row(v, lane);
+    if (i < C.trows) C.T[(int64_t)i * C.nG + g] = acc[v];
+  }
+}
+
+// Gram partial: rows c of sample b over one K segment, lower triangle of the nc x nc
+// block.  Every wave contracts its quarter of each staged panel (contract_tile's
+// narrow mode); the four partials are summed in a fixed order.
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_gram(CovArgs args) {
+  __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
+  const int task = blockIdx.x;
+  const CovJobDev& C = args.job[cov_find_job(args.g_end, args.njobs, task)];
+  const int64_t local = task - C.g_begin;
+  const int64_t b = local / C.nseg;
+  const int seg = (int)(local % C.nseg);
+  const int nc = args.nc;
+  const int64_t K = (int64_t)C.nA * C.nG;
+  const int64_t k0 = (int64_t)seg * GSEG, k1 = min(K, k0 + GSEG);
+  const OpDev t = channel_op(C.T + b * nc * K, K, nc, K);
+  floatx16 acc;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+  contract_tile<KFAC_CHANNEL, KFAC_CHANNEL>(t, 0, t, 0, k0, k1, true, true, lds, acc, true);
+  // (contract_tile leaves through a barrier: lds is free)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr int RP = 33;
+  static_assert(4 * 32 * RP <= 4 * PANEL, "wave partials fit the staging buffer");
+#pragma unroll
+  for (int v = 0; v < 16; ++v) lds[(wave * 32 + acc_row(v, lane)) * RP + (lane & 31)] = acc[v];
+  __syncthreads();
+  float* part = C.partial + local * nc * nc;
+  for (int e = threadIdx.x; e < nc * nc; e += NTHREADS) {
+    const int c = e / nc, c2 = e - c * nc;
+    if (c2 > c) continue;
+    const int o = c * RP + c2;
+    part[e] = (lds[o] + lds[32 * RP + o]) + (lds[64 * RP + o] + lds[96 * RP + o]);
+  }
+}
+
+// cov[b] (+)= sum over jobs (in job order) of the segment partials (in segment order),
+// fp64; lower triangle mirrored.
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_reduce(CovArgs args) {
+  const int64_t b = blockIdx.x;
+  const int nc = args.nc, n2 = nc * nc;
+  float* cov = args.cov + b * n2;
+  for (int e = threadIdx.x; e < n2; e += NTHREADS) {
+    const int c = e / nc, c2 = e - c * nc;
+    if (c2 > c) continue;
+    double total = 0.0;
+    for (int j = 0; j < args.njobs; ++j) {
+      const CovJobDev& C = args.job[j];
+      const float* part = C.partial + b * C.nseg * n2 + e;
+      double s = 0.0;
+      for (int i = 0; i < C.nseg; ++i) s += (double)part[(int64_t)i * n2];
+      total += s;
+    }
+    const float v = args.accumulate ? (float)((double)cov[e] + total) : (float)total;
+    cov[e] = v;
+    cov[c2 * nc + c] = v;
+  }
+}
+
+static size_t cov_t_bytes(const kfac_cov_job& j, int64_t rows) {
+  return align_up((size_t)rows * (size_t)j.nA * (size_t)j.nG * sizeof(float), 256);
+}
+static int64_t cov_nseg(const kfac_cov_job& j) { return cdiv((int64_t)j.nA * j.nG, GSEG); }
+static size_t cov_partial_bytes(const kfac_cov_job& j, int64_t nb, int nc) {
+  return align_up((size_t)(nb * cov_nseg(j)) * nc * nc * sizeof(float), 256);
+}
+static bool cov_job_ok(const kfac_cov_job& q) {
+  return q.J && q.K1 && q.K2 && q.nA > 0 && q.nG > 0 && q.ld1 >= q.nA && q.ld2 >= q.nG &&
+         q.ldJ >= (int64_t)q.nA * q.nG;
+}
+
+}  // namespace kfac
+
+using namespace kfac;
+
+extern "C" size_t kfac_kron_cov_workspace_bytes(const kfac_cov_job* jobs, int njobs, int64_t nb,
+                                                int nc) {
+  if (!jobs || njobs <= 0 || njobs > CMAXJ || nb <= 0 || nc <= 0 || nc > CMAXC) return 0;
+  size_t total = 0;
+  for (int i = 0; i < njobs; ++i) {
+    if (jobs[i].nA <= 0 || jobs[i].nG <= 0) return 0;
+    total += 2 * cov_t_bytes(jobs[i], nb * nc) + cov_partial_bytes(jobs[i], nb, nc);
+  }
+  return total;
+}
+
+extern "C" int kfac_kron_cov(const kfac_cov_job* jobs, int njobs, int64_t nb, int nc, int accumulate,
+                             float* cov, void* workspace, size_t workspace_bytes,
+                             kfac_stream_t stream) {
+  if (!jobs || njobs <= 0 || njobs > CMAXJ || nb <= 0 || nc <= 0 || nc > CMAXC || !cov)
+    return KFAC_EINVAL;
+  for (int i = 0; i < njobs; ++i)
+    if (!cov_job_ok(jobs[i])) return KFAC_EINVAL;
+  const int64_t lim = (int64_t)1 << 31;
+  if (nb >= lim / nc) return KFAC_EINVAL;
+  const int64_t rows = nb * nc;
+  CovArgs args{};
+  args.njobs = njobs;
+  args.nc = nc;
+  args.accumulate = accumulate;
+  args.nb = nb;
+  args.cov = cov;
+  int64_t nu = 0, nt = 0, ng = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const kfac_cov_job& q = jobs[i];
+    // the stacked operands are indexed with 32-bit columns: rows*nG and rows*nA (and
+    // with them every launch's task count) stay below 2^31
+    if (rows * q.nG >= lim - TILE || rows * q.nA >= lim - TILE) return KFAC_EINVAL;
+    CovJobDev& d = args.job[i];
+    d.J = q.J; d.K1 = q.K1; d.K2 = q.K2;
+    d.ldJ = q.ldJ; d.ld1 = q.ld1; d.ld2 = q.ld2;
+    d.nA = q.nA; d.nG = q.nG;
+    d.tg = (int)cdiv(q.nG, TILE);
+    d.nseg = (int)cov_nseg(q);
+    d.lower1 = q.lower1 != 0;
+    d.lower2 = q.lower2 != 0;
+    d.ucols = (int)(rows * q.nG);
+    d.trows = (int)(rows * q.nA);
+    d.u_begin = (int)nu; d.t_begin = (int)nt; d.g_begin = (int)ng;
+    nu += cdiv(q.nA, TILE) * cdiv(d.ucols, TILE);
+    nt += cdiv(d.trows, TILE) * d.tg;
+    ng += nb * d.nseg;
+    if (nu >= lim || nt >= lim || ng >= lim) return KFAC_EINVAL;
+    args.u_end[i] = (int)nu; args.t_end[i] = (int)nt; args.g_end[i] = (int)ng;
+  }
+  if (!workspace || workspace_bytes < kfac_kron_cov_workspace_bytes(jobs, njobs, nb, nc))
+    return KFAC_EWORKSPACE;
+  char* ws = (char*)workspace;
+  for (int i = 0; i < njobs; ++i) {
+    CovJobDev& d = args.job[i];
+    const size_t tb = cov_t_bytes(jobs[i], rows);
+    d.U = reinterpret_cast<float*>(ws); ws += tb;
+    d.T = reinterpret_cast<float*>(ws); ws += tb;
+    d.partial = reinterpret_cast<float*>(ws); ws += cov_partial_bytes(jobs[i], nb, nc);
+  }
+  args.nu = (int)nu; args.nt = (int)nt; args.ng = (int)ng;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kfac_cov_apply_u, dim3((unsigned)nu), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_apply_t, dim3((unsigned)nt), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_gram, dim3((unsigned)ng), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_reduce, dim3((unsigned)nb), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}

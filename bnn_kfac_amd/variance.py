@@ -6,9 +6,16 @@ sampling_free/regression/regression_ll_block.py:120-140 with one grouped device
 contraction (libkfac_hip `kfac_kron_quadform`) that never forms the Kronecker
 product.  The Jacobians J themselves stay host-side PyTorch autograd, exactly as
 the reference builds them (sampling_free/utils.py:221-226).
+
+The GLM predictive (glm_predictive / probit_predictive, further down) goes beyond the
+reference: logits and their full covariance under the KFAC posterior in closed form
+(`kfac_kron_cov`), where the reference samples weights and re-runs the network.
 """
 from __future__ import annotations
 
+import contextlib
+import math
+from collections import OrderedDict
 from typing import Iterable, List, Sequence, Tuple
 
 import numpy as np
@@ -88,6 +95,24 @@ def kron_quadform(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool = 
     return (out, v) if per_term else out
 
 
+@contextlib.contextmanager
+def hooks_suspended(model: torch.nn.Module):
+    """KFAC's module hooks (record capture) must not fire inside the functorch
+    transforms: suspend every module hook of `model` inside the block, then restore
+    the exact hook dictionaries."""
+    kinds = ("_forward_hooks", "_forward_pre_hooks", "_backward_hooks", "_backward_pre_hooks")
+    saved = [(m, [getattr(m, k) for k in kinds]) for m in model.modules()]
+    for m, _ in saved:
+        for k in kinds:
+            setattr(m, k, OrderedDict())
+    try:
+        yield
+    finally:
+        for m, dicts in saved:
+            for k, d in zip(kinds, dicts):
+                setattr(m, k, d)
+
+
 def layer_jacobians(output: Tensor, layers: Sequence[torch.nn.Module], grad_outputs: Tensor) -> List[Tensor]:
     """[J_i] for several layers from ONE backward pass: the same vectors as the
     reference's per-parameter `gradient` calls (classification_ll_block.py:128-130,
@@ -131,8 +156,6 @@ def per_sample_predictive_std(kfac, x: Tensor, layers: Iterable = None, chunk: i
     the whole chunk is contracted by a single kfac_kron_quadform launch (nb rows per
     layer) instead of a Python loop of single-image backward passes.  Returns (N,) fp32.
     """
-    from collections import OrderedDict
-
     from torch.func import functional_call, grad, vmap
     model = kfac.model
     if layers is None:
@@ -140,20 +163,8 @@ def per_sample_predictive_std(kfac, x: Tensor, layers: Iterable = None, chunk: i
     layers = list(layers)
     names = {id(p): n for n, p in model.named_parameters()}
     pnames = [[names[id(p)] for p in layer.parameters()] for layer in layers]
-    # KFAC's module hooks (record capture) must not fire inside the functorch
-    # transforms: suspend every module hook for this call, then restore the exact
-    # hook dictionaries
-    kinds = ("_forward_hooks", "_forward_pre_hooks", "_backward_hooks", "_backward_pre_hooks")
-    saved = [(m, [getattr(m, k) for k in kinds]) for m in model.modules()]
-    for m, _ in saved:
-        for k in kinds:
-            setattr(m, k, OrderedDict())
-    try:
+    with hooks_suspended(model):
         return _per_sample_std(kfac, model, layers, pnames, x, chunk, functional_call, grad, vmap)
-    finally:
-        for m, dicts in saved:
-            for k, d in zip(kinds, dicts):
-                setattr(m, k, d)
 
 
 def _per_sample_std(kfac, model, layers, pnames, x, chunk, functional_call, grad, vmap):
@@ -179,6 +190,158 @@ def _per_sample_std(kfac, model, layers, pnames, x, chunk, functional_call, grad
             terms.append((J, LA, LG))
         out.append(kron_quadform(terms, lower=True, abs_sum=True))
     return torch.cat(out)
+
+
+# ------------------------------------------------------------ GLM predictive
+# The closed-form counterpart of the sampling loop (sampling/classification_sampling.py:
+# 71-79: sample_and_replace + a forward pass per draw): logits f(x) and their full
+# covariance J Sigma J^T under the Gaussian KFAC.sample draws from, by kfac_kron_cov.
+MAX_COV_CLASSES = 32
+
+
+def posterior_jacobian(dW: Tensor, db: Tensor = None, batch_dims: int = None) -> Tensor:
+    """Jacobian rows in the posterior's order: KFAC.sample draws S (nA x nG) and adds
+    S^T into [W | b], so row M (nA x nG, flat index a*nG + g) has M[a][g] = dW[g][a]
+    for a < wcols and M[nA-1][g] = db[g].
+
+    dW: (..., nG, *rest) (a Conv2d weight is flattened per output channel, F.unfold's
+    column order), db: (..., nG) or None.  `batch_dims` leading dimensions are kept
+    (default: db.dim() - 1, or 0 without db).  Returns (..., nA*nG).  Pure torch.
+    """
+    if batch_dims is None:
+        batch_dims = db.dim() - 1 if db is not None else 0
+    if dW.dim() < batch_dims + 1:
+        raise ValueError(f"dW {tuple(dW.shape)} has no nG dimension after {batch_dims} batch dimensions")
+    lead = tuple(dW.shape[:batch_dims])
+    nG = dW.shape[batch_dims]
+    M = dW.reshape(*lead, nG, -1).transpose(-1, -2)  # (..., wcols, nG)
+    if db is not None:
+        if tuple(db.shape) != lead + (nG,):
+            raise ValueError(f"db {tuple(db.shape)} does not match dW {tuple(dW.shape)}")
+        M = torch.cat([M, db.unsqueeze(-2)], dim=-2)
+    return M.reshape(*lead, -1)
+
+
+def _cov_rows(J: Tensor, K: int):
+    """(J as (nb, nc, K) with rows r = b*nc + c a constant stride apart, that stride)."""
+    J = J.detach()
+    if J.dim() == 2:
+        J = J.unsqueeze(0)
+    if J.dim() != 3 or J.shape[2] != K:
+        raise ValueError(f"J {tuple(J.shape)}: expected (nb, nc, {K}) or (nc, {K})")
+    nb, nc = J.shape[0], J.shape[1]
+    ld = J.stride(1) if nc > 1 else (J.stride(0) if nb > 1 else K)
+    if J.stride(2) != 1 or ld < K or (nb > 1 and J.stride(0) != nc * ld):
+        J, ld = J.contiguous(), K
+    return J, ld
+
+
+def kron_covariance(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool = True,
+                    max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """cov[b, c, c'] = sum_l J_l[b, c] (K1_l K1_l^T kron K2_l K2_l^T) J_l[b, c']^T.
+
+    terms: [(J_l, K1_l, K2_l)], J (nb, nc, nA*nG) or (nc, nA*nG) in the POSTERIOR's order
+    (posterior_jacobian), K1 (nA x nA), K2 (nG x nG); `lower` marks them lower-triangular
+    (KFAC.invert's Cholesky factors).  Returns (nb, nc, nc) fp32, every block bitwise
+    symmetric.  More than 8 terms fold in groups of 8; the samples are cut into chunks
+    that need at most `max_workspace_bytes` of scratch each (a sample's block depends
+    on that sample only, so chunking does not change a bit).
+    """
+    if not terms:
+        raise ValueError("no terms")
+    keep, jobs = [], []
+    nb = nc = None
+    for J, K1, K2 in terms:
+        if K1.dim() != 2 or K2.dim() != 2 or K1.shape[0] != K1.shape[1] or K2.shape[0] != K2.shape[1]:
+            raise ValueError(f"K1 {tuple(K1.shape)} / K2 {tuple(K2.shape)}: expected square matrices")
+        nA, nG = K1.shape[0], K2.shape[0]
+        J3, ld = _cov_rows(J, nA * nG)
+        if nb is None:
+            nb, nc = J3.shape[0], J3.shape[1]
+        elif (J3.shape[0], J3.shape[1]) != (nb, nc):
+            raise ValueError("all terms need the same (nb, nc)")
+        if nc > MAX_COV_CLASSES:
+            raise ValueError(f"kron_covariance handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        for t, what in ((J3, "J"), (K1, "K1"), (K2, "K2")):
+            N.require_device(t, what)
+        K1c = K1.detach() if K1.stride(-1) == 1 else K1.detach().contiguous()
+        K2c = K2.detach() if K2.stride(-1) == 1 else K2.detach().contiguous()
+        keep.extend([J3, K1c, K2c])
+        jobs.append((J3.data_ptr(), ld, nA, nG, K1c.data_ptr(), K1c.stride(0), K2c.data_ptr(),
+                     K2c.stride(0), int(lower), int(lower)))
+    out = torch.empty(nb, nc, nc, dtype=torch.float32, device=keep[0].device)
+    if nb == 0:
+        return out
+    groups = [jobs[i:i + 8] for i in range(0, len(jobs), 8)]
+
+    def need(n):
+        return max(N.kron_cov_workspace_bytes([N.CovJob(*j) for j in g], n, nc) for g in groups)
+
+    step = nb
+    while step > 1 and need(step) > max_workspace_bytes:
+        step = max(1, min(step - 1, step * max_workspace_bytes // need(step)))
+    if need(step) > max_workspace_bytes:
+        raise ValueError(f"one sample needs {need(1)} workspace bytes, max_workspace_bytes is "
+                         f"{max_workspace_bytes}")
+    for b0 in range(0, nb, step):
+        n = min(step, nb - b0)
+        for gi, g in enumerate(groups):
+            arr = [N.CovJob(j[0] + 4 * b0 * nc * j[1], *j[1:]) for j in g]
+            N.kron_cov(arr, n, nc, out[b0:b0 + n], accumulate=gi > 0)
+    return out
+
+
+def output_jacobians(model: torch.nn.Module, layers: Sequence[torch.nn.Module], x: Tensor):
+    """(logits (n, nc), [J_l (n, nc, nA_l*nG_l)]): every sample's Jacobian of the model's
+    outputs w.r.t. each layer's [W | b], in the posterior's order (posterior_jacobian),
+    from one vmapped reverse-mode Jacobian (torch.func).  Module hooks are suspended."""
+    from torch.func import functional_call, jacrev, vmap
+    names = {id(p): n for n, p in model.named_parameters()}
+    pnames = []
+    for layer in layers:
+        bias = getattr(layer, "bias", None)
+        pnames.append((names[id(layer.weight)], names[id(bias)] if bias is not None else None))
+    params = {n: p.detach() for n, p in model.named_parameters()}
+    buffers = {n: b for n, b in model.named_buffers()}
+    theta = {n: params[n] for group in pnames for n in group if n is not None}
+
+    def outputs(th, xb):
+        full = dict(params)
+        full.update(th)
+        y = functional_call(model, (full, buffers), (xb.unsqueeze(0),))[0].reshape(-1)
+        return y, y
+
+    with hooks_suspended(model):
+        jac, logits = vmap(jacrev(outputs, has_aux=True), in_dims=(None, 0))(theta, x)
+    Js = [posterior_jacobian(jac[w], jac[b] if b is not None else None, batch_dims=2)
+          for w, b in pnames]
+    return logits.detach(), Js
+
+
+def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64):
+    """The linearised (GLM) predictive of `kfac.model` under the KFAC posterior
+    (KFAC.invert's factors, the Gaussian KFAC.sample draws from): (logits (N, nc),
+    cov (N, nc, nc)) with cov = sum_l J_l (L_A L_A^T kron L_G L_G^T) J_l^T, in chunks
+    of `chunk` samples.  No sampling loop, no weight replacement; a regression net
+    with one output has its predictive variance in cov[:, 0, 0]."""
+    model = kfac.model
+    if layers is None:
+        layers = [m for m in list(model.modules())[1:] if m in kfac.state]
+    layers = list(layers)
+    inv = kfac.inv_state
+    logits, covs = [], []
+    for c0 in range(0, x.shape[0], chunk):
+        f, Js = output_jacobians(model, layers, x[c0:c0 + chunk])
+        logits.append(f)
+        covs.append(kron_covariance([(J, *inv[layer]) for layer, J in zip(layers, Js)], lower=True))
+    return torch.cat(logits), torch.cat(covs)
+
+
+def probit_predictive(logits: Tensor, cov: Tensor) -> Tensor:
+    """softmax(logits / sqrt(1 + pi/8 * diag(cov))): the probit approximation of
+    E[softmax(f)] for f ~ N(logits, cov).  Pure torch."""
+    var = torch.diagonal(cov, dim1=-2, dim2=-1)
+    return torch.softmax(logits / torch.sqrt(1.0 + (math.pi / 8.0) * var), dim=-1)
 
 
 def argmax_grad_outputs(pred_mean: Tensor) -> Tensor:

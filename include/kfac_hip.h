@@ -221,6 +221,33 @@ KFAC_API size_t kfac_quadform_workspace_bytes(const kfac_quad_job* jobs, int njo
 KFAC_API int kfac_kron_quadform(const kfac_quad_job* jobs, int njobs, int64_t nb, int abs_sum, float* out,
                        void* workspace, size_t workspace_bytes, kfac_stream_t stream);
 
+/* ------------------------------------------------- GLM predictive covariance
+ * The full output covariance of the linearised (GLM) predictive under the posterior
+ * kfac_sample draws from: vec(S) (S = K1 z K2^T, index a*nG + g) has covariance
+ * K1 K1^T (x) K2 K2^T, so with M_r = Jacobian row r = b*nc + c (sample b, output c)
+ * viewed (nA x nG) row-major,
+ *   cov[b][c][c'] = sum_j < K1_j^T M_{b,c} K2_j , K1_j^T M_{b,c'} K2_j >_F
+ * without forming the Kronecker product.  M is in the POSTERIOR's order
+ * (M[a][g] = dW[g][a], M[nA-1][g] = db[g]), not kfac_quad_job's reference order.
+ * cov is nb x nc x nc, each block bitwise symmetric; partial sums are reduced in a
+ * fixed order in fp64 (no atomics): two calls give identical bits, and a sample's block
+ * depends on that sample's rows only.  accumulate: cov += the sum, else cov = it.
+ * At most 8 jobs and nc <= 32 per call.                                        */
+typedef struct kfac_cov_job {
+  const float* J; /* row r = b*nc + c at J + r*ldJ: nA*nG elements, index a*nG + g */
+  int64_t ldJ;
+  int32_t nA, nG;
+  const float* K1;
+  int64_t ld1;
+  const float* K2;
+  int64_t ld2;
+  int32_t lower1, lower2; /* K1 / K2 lower-triangular: their zero K-range is skipped */
+} kfac_cov_job;
+
+KFAC_API size_t kfac_kron_cov_workspace_bytes(const kfac_cov_job* jobs, int njobs, int64_t nb, int nc);
+KFAC_API int kfac_kron_cov(const kfac_cov_job* jobs, int njobs, int64_t nb, int nc, int accumulate,
+                  float* cov, void* workspace, size_t workspace_bytes, kfac_stream_t stream);
+
 /* -------------------------------------------------------- posterior samples
  * out_j = (LA_j Z_j LG_j^T)^T, shape (nG x nA): KFAC.sample, curvatures.py:400-405,
  * with Z (nA x nG row-major) supplied by the caller (torch.randn, the reference's

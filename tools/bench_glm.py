@@ -1,0 +1,132 @@
+"""Time the GLM predictive (variance.kron_covariance / glm_predictive).
+
+Workloads (random init, KFAC factors accumulated over synthetic batches, inverted at
+(0.04, 200)):
+  mlp       : the MNIST MLP 784-128-10 (layers 785x128, 129x10), nb = 64, nc = 10
+  basenet15k: BaseNet_15k's four layers (26x5, 126x10, 161x80, 81x10), nb = 256, nc = 10
+
+Per workload, on the same Jacobians and factors:
+  cov_ms        : kron_covariance (kfac_kron_cov) alone
+  torch_cov_ms  : the same contraction composed from torch ops on the same GPU,
+                  T = L_A^T @ M @ L_G, cov = sum_l T.flatten(2) @ T.flatten(2).mT
+  cpu_cov_ms    : that composition in fp32 on the host, 16 threads
+  glm_ms        : glm_predictive end to end (vmapped Jacobians + kron_covariance)
+  torch_glm_ms  : the same Jacobians + the torch composition
+GPU times are HIP-event times of single calls after a warm-up, medians over `--reps`
+calls.  apply_flops / gram_bytes are the algorithmic work (2 nA^2 nG + 2 nA nG^2 per
+row, halved for the skipped triangle; T read once) for a roofline over kernel times
+taken in a profiler run of `--only cov`.  Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from bnn_kfac_amd import _native as N  # noqa: E402
+from bnn_kfac_amd.curvatures import KFAC  # noqa: E402
+from bnn_kfac_amd.variance import glm_predictive, kron_covariance, output_jacobians  # noqa: E402
+
+
+def mlp():
+    return nn.Sequential(nn.Linear(784, 128), nn.ReLU(), nn.Linear(128, 10)), (784,), 64
+
+
+def basenet15k():
+    return nn.Sequential(nn.Conv2d(1, 5, 5), nn.ReLU(), nn.MaxPool2d(2), nn.Conv2d(5, 10, 5), nn.ReLU(),
+                         nn.MaxPool2d(2), nn.Flatten(), nn.Linear(160, 80), nn.ReLU(),
+                         nn.Linear(80, 10)), (1, 28, 28), 256
+
+
+def event_ms(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return statistics.median(times)
+
+
+def torch_cov(terms):
+    cov = 0
+    for J, LA, LG in terms:
+        nA, nG = LA.shape[0], LG.shape[0]
+        T = (LA.T @ J.view(J.shape[0], J.shape[1], nA, nG) @ LG).flatten(2)
+        cov = cov + T @ T.mT
+    return cov
+
+
+def run(name, make, dev, args):
+    torch.manual_seed(0)
+    net, xshape, nb = make()
+    net = net.to(dev)
+    kfac = KFAC(net)
+    for _ in range(3):
+        x = torch.rand(256, *xshape, device=dev)
+        logits = net(x)
+        y = torch.distributions.Categorical(logits=logits).sample()
+        net.zero_grad()
+        nn.functional.cross_entropy(logits, y).backward()
+        kfac.update(256)
+    kfac.invert(0.04, 200)
+    layers = [m for m in list(net.modules())[1:] if m in kfac.state]
+    x = torch.rand(nb, *xshape, device=dev)
+    _, Js = output_jacobians(net, layers, x)
+    terms = [(J.contiguous(), *kfac.inv_state[l]) for l, J in zip(layers, Js)]
+    nc = Js[0].shape[1]
+    res = {"nb": nb, "nc": nc, "layers": [[t[1].shape[0], t[2].shape[0]] for t in terms]}
+    res["apply_flops"] = sum(nb * nc * (a * a * g + a * g * g) for a, g in res["layers"])
+    res["gram_bytes"] = sum(nb * nc * a * g * 4 for a, g in res["layers"])
+    res["cov_ms"] = event_ms(lambda: kron_covariance(terms), args.warmup, args.reps)
+    if args.only == "cov":
+        return res
+    res["torch_cov_ms"] = event_ms(lambda: torch_cov(terms), args.warmup, args.reps)
+    got, want = kron_covariance(terms), torch_cov(terms)
+    res["max_diff_vs_torch_over_max"] = float((got - want).abs().max() / want.abs().max())
+    res["glm_ms"] = event_ms(lambda: glm_predictive(kfac, x, chunk=nb), 2, max(3, args.reps // 4))
+
+    def torch_glm():
+        _, Jt = output_jacobians(net, layers, x)
+        return torch_cov([(J, *kfac.inv_state[l]) for l, J in zip(layers, Jt)])
+
+    res["torch_glm_ms"] = event_ms(torch_glm, 2, max(3, args.reps // 4))
+    torch.set_num_threads(16)
+    cpu_terms = [tuple(t.cpu() for t in term) for term in terms]
+    torch_cov(cpu_terms)
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        torch_cov(cpu_terms)
+        times.append((time.perf_counter() - t0) * 1e3)
+    res["cpu_cov_ms"] = statistics.median(times)
+    res["cpu_threads"] = torch.get_num_threads()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--only", choices=["all", "cov"], default="all",
+                    help="cov: kron_covariance alone (A/B builds, profiler runs)")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    out = {"workload": "GLM predictive covariance", "lib": N.LIB_PATH}
+    for name, make in (("mlp", mlp), ("basenet15k", basenet15k)):
+        out[name] = run(name, make, dev, args)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
