@@ -9,7 +9,9 @@
 // inverse, instead of getrf/getri + potrf; all arithmetic in fp64 (cond(R)
 // reaches ~1e5 on the MLP).
 //
-// Blocked over 64x64 fp64 tiles; every launch is grouped over ALL factors:
+// Blocked over square fp64 tiles; every launch is grouped over ALL factors of a call
+// (IMAXJ at a time).  The tile edge of a call is its path (small_tiles()):
+//   32-tiles, merged steps (invert_merged.hip):
 //   inv_step(-1)    build R' = P R P (damped, symmetrised, identity padded), Z = 0,
 //                   info = 0; its workgroup 0 factors tile (0,0): X[0][0] = chol^{-1}
 //   for k = 0..T-1: inv_step(k), ONE launch per step, the panel folded in:
@@ -19,45 +21,44 @@
 //                   X[k][j]   = X[k][k] Z[k][j] -> W[k][j] (final, j < k)
 //                   and the block owning (k+1,k+1) factors it right after its
 //                   update -> X[k+1][k+1] (one factorisation per step).
-//   [inv_xtx]       Y = X^T X (only for the full-inverse output)
 //   L[i][j] = X[n-1-j][n-1-i] (fp32) is written by the step that finalises each X
-//   tile (upper zero blocks by step -1): no separate output pass.  The full-inverse
-//   output (R^{-1} = P Y P) and the two-launch path (below) keep inv_out.
+//   tile (upper zero blocks by step -1): no separate output pass.
+//   64-tiles, blocked updates (invert_blocked.hip): inv_build, then per step one
+//   inv_panel and the updates applied per block of panels (inv_inner, inv_bulk,
+//   inv_diag).
+//   [inv_xtx]       Y = X^T X (only for the full-inverse output)
+//   The full-inverse output (R^{-1} = P Y P) and the blocked path keep inv_out.
 // Z (the partially eliminated identity) lives in X's lower tiles.  Tile GEMMs
-// use v_mfma_f64_16x16x4_f64; the 64x64 diagonal factorisation is blocked by 16
-// (one wave eliminates each 16x16 diagonal block, MFMA for the rest).
-#include <math.h>
-
-#include <string.h>
-
+// use v_mfma_f64_16x16x4_f64; the diagonal tile's factorisation is blocked by 16
+// (one wave eliminates each 16x16 diagonal block, MFMA for the rest): the shared
+// device code is invert_tiles.inc.
 #include <algorithm>
-#include <mutex>
-#include <vector>
 
 #include "kfac_common.h"
 
 namespace kfac {
-namespace t64 {  // 64x64 fp64 tiles: the two-launch path of large factors (> 1536)
-constexpr int NB = 64;
-constexpr int MERGE_T = 24;
-#include "invert_tiles.inc"
-}  // namespace t64
-namespace t32 {  // 32x32 fp64 tiles: latency-bound factors (<= 1536), see below
-constexpr int NB = 32;
-constexpr int MERGE_T = 48;
-#include "invert_tiles.inc"
+// a group's (at most IMAXJ jobs, regions packed from `ws`) launches of one phase, and a
+// job's workspace bytes, per path
+namespace t32 {  // invert_merged.hip
+size_t job_ws(const kfac_invert_job& j);
+int invert_group(const kfac_invert_job* jobs, int njobs, char* ws, int32_t* info, hipStream_t s, int phase);
+void release_graphs();
 }  // namespace t32
+namespace t64 {  // invert_blocked.hip
+size_t job_ws(const kfac_invert_job& j);
+int invert_group(const kfac_invert_job* jobs, int njobs, char* ws, int32_t* info, hipStream_t s, int phase);
+void release_look_ahead();
+}  // namespace t64
 }  // namespace kfac
-
 
 using namespace kfac;
 
-// Tile edge of a call: 32x32 fp64 tiles when every factor is at most 1536 (the merged
-// one-launch steps: latency-bound, and a 32-tile workgroup needs 29 KB of LDS, so it
-// fits on a CU beside the 4 resident workgroups of a running SYRK launch, which leave
-// 32 KB: the inversion overlaps the next data pass instead of waiting for its
-// launches to drain); 64x64 tiles for larger factors (throughput-bound two-launch
-// steps).
+// Tile edge, and with it the path, of a call: 32x32 fp64 tiles when every factor is at
+// most 1536 (the merged one-launch steps: latency-bound, and a 32-tile workgroup needs
+// 29 KB of LDS, so it fits on a CU beside the 4 resident workgroups of a running SYRK
+// launch, which leave 32 KB: the inversion overlaps the next data pass instead of
+// waiting for its launches to drain); 64x64 tiles for larger factors (the
+// throughput-bound blocked updates).
 static bool small_tiles(const kfac_invert_job* jobs, int njobs) {
   int m = 0;
   for (int i = 0; i < njobs; ++i) m = std::max(m, (int)jobs[i].n);
@@ -93,8 +94,6 @@ static int check_jobs(const kfac_invert_job* jobs, int njobs) {
 static int invert_phase(const kfac_invert_job* jobs, int njobs, void* workspace, int32_t* info,
                         hipStream_t stream, int phase) {
   const bool small = small_tiles(jobs, njobs);
-  constexpr int IMAXJ = t64::IMAXJ;
-  static_assert(t32::IMAXJ == t64::IMAXJ, "group size");
   char* ws = (char*)workspace;
   for (int g = 0; g < njobs; g += IMAXJ) {
     const int ng = std::min(IMAXJ, njobs - g);
@@ -153,12 +152,11 @@ extern "C" int kfac_invert(const kfac_invert_job* jobs, int njobs, void* workspa
   return kfac_invert_ex(jobs, njobs, workspace, workspace_bytes, info, nullptr, stream);
 }
 
-// the inversion's cached hipGraphs (both tile sizes); see kfac_release (capi.hip)
+// the merged path's cached hipGraphs and the blocked path's helper streams; see
+// kfac_release (capi.hip)
 int kfac_release_graphs() {
-  t64::release_graphs();
   t32::release_graphs();
   t64::release_look_ahead();
-  t32::release_look_ahead();
   return KFAC_OK;
 }
 

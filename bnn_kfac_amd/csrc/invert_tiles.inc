@@ -1,8 +1,9 @@
-// Tile-size generic part of invert.hip, included once per fp64 tile edge NB (32 or 64)
-// inside a namespace that defines NB and MERGE_T (the most tiles per edge that take
-// the merged one-launch step).
+// Tile-size generic part of the fp64 inversion: included by invert_merged.hip (NB = 32)
+// and invert_blocked.hip (NB = 64) inside namespace kfac::t32 / kfac::t64, after NB.
+// Device: tile access, MFMA tile products, the diagonal factorisation, the build of R',
+// the output blocks, and the two kernels both paths launch (inv_xtx, inv_out).
+// Host: workspace layout, InvArgs of a group, the grouped launch.
 constexpr int DP = NB + 4;  // LDS pitch (doubles): conflict-free 16-byte MFMA operand reads (mfma_block)
-constexpr int IMAXJ = 8;
 constexpr int NBB = NB / 16;           // 16x16 MFMA blocks per tile edge
 constexpr int BPW = NBB * NBB / 4;     // blocks of a tile product per wave (4 or 1)
 constexpr int RSTEP = NTHREADS / NB;   // tile rows covered by one pass of the workgroup
@@ -21,15 +22,15 @@ struct InvJobDev {
   int* info;
   double scale, shift;
   int n, T, Np, kind;
-  int xw;      // final strictly-lower X tiles in W (merged step) instead of X
-  int fout;    // merged step, inverse-Cholesky output: the steps write L (no inv_out)
+  int xw;      // final strictly-lower X tiles in W (merged path) instead of X
+  int fout;    // merged path, inverse-Cholesky output: the steps write L (no inv_out)
 };
 
 struct InvArgs {
   int njobs;
   int step;
   int tpw;         // inv_step: tasks per workgroup (1, or 2: see inv_step)
-  int kend;        // blocked two-launch path: end of the panel block [step, kend)
+  int kend;        // blocked path: end of the panel block [step, kend)
   int ksplit;      // inv_bulk parts 1 / 2: end of the NEXT panel block [kend, ksplit)
   int part;        // inv_bulk: 0 every tile, 1 the next block's, 2 the rest (look-ahead)
   int begin[IMAXJ + 1];
@@ -46,102 +47,42 @@ __device__ __forceinline__ double* tile_ptr(double* base, int Np, int ti, int tj
   return base + ((int64_t)ti * NB) * Np + (int64_t)tj * NB;
 }
 
-// Global access to the W / X workspace tiles.  C = true: the agent-scope atomic
-// form (tiles handed between workgroups of one launch); C = false: plain accesses
-// (every caller here: tiles cross kernel boundaries only).
-typedef __attribute__((address_space(1))) double gdouble;
-typedef __attribute__((address_space(1))) unsigned gunsigned;
-template <bool C>
-__device__ __forceinline__ double gld(const double* p) {
-  if constexpr (C)
-    return __hip_atomic_load((gdouble*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else
-    return *p;
-}
-template <bool C>
-__device__ __forceinline__ void gst(double* p, double v) {
-  if constexpr (C)
-    __hip_atomic_store((gdouble*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else
-    *p = v;
-}
-
-// All 16 loads of a thread are issued before the first LDS write (a rolled loop
-// would serialise 16 global-memory round trips).
-template <bool C = false>
-__device__ __forceinline__ void load_tile(double* lds, const double* g, int Np);
-template <bool C = false>
-__device__ __forceinline__ void load_tiles(double* l0, const double* g0, double* l1, const double* g1,
-                                           double* l2, const double* g2, int Np);
-template <bool C>
-__device__ __forceinline__ void load_tile(double* lds, const double* g, int Np) {
-  if constexpr (!C) {
-    load_tiles<false>(lds, g, nullptr, nullptr, nullptr, nullptr, Np);
-    return;
-  }
-  constexpr int PER = NB * NB / NTHREADS;
-  const int c = threadIdx.x % NB, r0 = threadIdx.x / NB;
-  double v[PER];
-#pragma unroll
-  for (int q = 0; q < PER; ++q) v[q] = gld<C>(g + (int64_t)(r0 + RSTEP * q) * Np + c);
-#pragma unroll
-  for (int q = 0; q < PER; ++q) lds[(r0 + RSTEP * q) * DP + c] = v[q];
-}
-
-// Up to three tiles with every load in flight together (one memory round trip
-// instead of one per tile); null destinations are skipped.
-template <bool C>
+// Up to three W / X workspace tiles into LDS with every load in flight together (one
+// memory round trip instead of one per tile, and all of a thread's loads issued before
+// its first LDS write); null destinations are skipped.  Plain accesses (tiles cross
+// kernel boundaries only): 16-byte loads and LDS stores, two doubles per lane.
 __device__ __forceinline__ void load_tiles(double* l0, const double* g0, double* l1, const double* g1,
                                            double* l2, const double* g2, int Np) {
-  if constexpr (!C) {
-    // plain accesses: 16-byte loads and LDS stores (two doubles per lane; half the
-    // memory instructions of the 8-byte form)
-    typedef double d2 __attribute__((ext_vector_type(2)));
-    constexpr int LPR = NB / 2;                  // lanes per tile row
-    constexpr int RS2 = NTHREADS / LPR;          // rows per pass
-    constexpr int PER2 = NB * NB / (2 * NTHREADS);
-    const int c = 2 * (threadIdx.x % LPR), r0 = threadIdx.x / LPR;
-    d2 v0[PER2], v1[PER2], v2[PER2];
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  constexpr int LPR = NB / 2;                  // lanes per tile row
+  constexpr int RS2 = NTHREADS / LPR;          // rows per pass
+  constexpr int PER2 = NB * NB / (2 * NTHREADS);
+  const int c = 2 * (threadIdx.x % LPR), r0 = threadIdx.x / LPR;
+  d2 v0[PER2], v1[PER2], v2[PER2];
 #pragma unroll
-    for (int q = 0; q < PER2; ++q) {
-      const int64_t off = (int64_t)(r0 + RS2 * q) * Np + c;
-      v0[q] = *reinterpret_cast<const d2*>(g0 + off);
-      if (l1) v1[q] = *reinterpret_cast<const d2*>(g1 + off);
-      if (l2) v2[q] = *reinterpret_cast<const d2*>(g2 + off);
-    }
-#pragma unroll
-    for (int q = 0; q < PER2; ++q) {
-      const int o = (r0 + RS2 * q) * DP + c;
-      *reinterpret_cast<d2*>(l0 + o) = v0[q];
-      if (l1) *reinterpret_cast<d2*>(l1 + o) = v1[q];
-      if (l2) *reinterpret_cast<d2*>(l2 + o) = v2[q];
-    }
-    return;
-  }
-  constexpr int PER = NB * NB / NTHREADS;
-  const int c = threadIdx.x % NB, r0 = threadIdx.x / NB;
-  double v0[PER], v1[PER], v2[PER];
-#pragma unroll
-  for (int q = 0; q < PER; ++q) {
-    const int64_t off = (int64_t)(r0 + RSTEP * q) * Np + c;
-    v0[q] = gld<C>(g0 + off);
-    if (l1) v1[q] = gld<C>(g1 + off);
-    if (l2) v2[q] = gld<C>(g2 + off);
+  for (int q = 0; q < PER2; ++q) {
+    const int64_t off = (int64_t)(r0 + RS2 * q) * Np + c;
+    v0[q] = *reinterpret_cast<const d2*>(g0 + off);
+    if (l1) v1[q] = *reinterpret_cast<const d2*>(g1 + off);
+    if (l2) v2[q] = *reinterpret_cast<const d2*>(g2 + off);
   }
 #pragma unroll
-  for (int q = 0; q < PER; ++q) {
-    const int o = (r0 + RSTEP * q) * DP + c;
-    l0[o] = v0[q];
-    if (l1) l1[o] = v1[q];
-    if (l2) l2[o] = v2[q];
+  for (int q = 0; q < PER2; ++q) {
+    const int o = (r0 + RS2 * q) * DP + c;
+    *reinterpret_cast<d2*>(l0 + o) = v0[q];
+    if (l1) *reinterpret_cast<d2*>(l1 + o) = v1[q];
+    if (l2) *reinterpret_cast<d2*>(l2 + o) = v2[q];
   }
 }
 
-template <bool C = false>
+__device__ __forceinline__ void load_tile(double* lds, const double* g, int Np) {
+  load_tiles(lds, g, nullptr, nullptr, nullptr, nullptr, Np);
+}
+
 __device__ __forceinline__ void store_tile(double* g, const double* lds, int Np) {
   for (int e = threadIdx.x; e < NB * NB; e += NTHREADS) {
     const int r = e / NB, c = e % NB;
-    gst<C>(g + (int64_t)r * Np + c, lds[r * DP + c]);
+    g[(int64_t)r * Np + c] = lds[r * DP + c];
   }
 }
 
@@ -200,24 +141,34 @@ __device__ __forceinline__ void gemm64(const double* A, const double* B, doublex
 }
 
 // global[tile](r, c) = alpha * acc (+ global if accumulate)   (acc from gemm64)
-template <bool C = false>
 __device__ __forceinline__ void store_acc_global(double* g, int Np, const doublex4 (&acc)[BPW],
                                                  double alpha, bool accumulate) {
   const int col = threadIdx.x & 15;
   auto at = [&](int x, int v) {
     return g + (int64_t)(16 * blk_r(x) + acc_row64(v)) * Np + 16 * blk_c(x) + col;
   };
-  // every old value loaded before the first store: atomic (C) accesses keep program
-  // order, so an interleaved load/store per element would serialise 16 round trips
+  // every old value loaded before the first store
   double old[BPW][4];
 #pragma unroll
   for (int x = 0; x < BPW; ++x)
 #pragma unroll
-    for (int v = 0; v < 4; ++v) old[x][v] = accumulate ? gld<C>(at(x, v)) : 0.0;
+    for (int v = 0; v < 4; ++v) old[x][v] = accumulate ? *at(x, v) : 0.0;
 #pragma unroll
   for (int x = 0; x < BPW; ++x)
 #pragma unroll
-    for (int v = 0; v < 4; ++v) gst<C>(at(x, v), old[x][v] + alpha * acc[x][v]);
+    for (int v = 0; v < 4; ++v) {
+      double* p = at(x, v);
+      *p = old[x][v] + alpha * acc[x][v];
+    }
+}
+
+// acc (gemm64 layout) -> LDS tile
+__device__ __forceinline__ void store_acc_lds(double* S, const doublex4 (&acc)[BPW]) {
+  const int col = threadIdx.x & 15;
+#pragma unroll
+  for (int x = 0; x < BPW; ++x)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) S[(16 * blk_r(x) + acc_row64(v)) * DP + 16 * blk_c(x) + col] = acc[x][v];
 }
 
 // 1/d: v_rcp_f64 + two Newton steps (~1 ulp) instead of the IEEE division sequence,
@@ -244,13 +195,12 @@ __device__ __forceinline__ double lane_value_rt(double x, int lane) {  // lane: 
 }
 
 // --------------------------------------------------------- diagonal factorisation
-// S (64x64 lower, LDS) -> Y = chol(S)^{-1} (lower, LDS); S is destroyed.
+// S (NB x NB lower, LDS) -> Y = chol(S)^{-1} (lower, LDS); S is destroyed.
 // Blocked by 16: wave 0 eliminates each 16x16 diagonal block [D | I] -> I_k =
 // D^{-1/2} L_unit^{-1}; the panel (C = S I_k^T, X_k = I_k Z_k) and the trailing /
 // Z updates are 16x16 MFMA blocks spread over the 4 waves.  dg (>= NB+352 doubles)
 // receives the pivots; its tail is scratch.
-template <int PARTS = 7>  // ablation (tools/microbench/diag_mb.hip): bit0 elimination, bit1 panel, bit2 trailing
-__device__ __forceinline__ void diag_factor(double* S, double* Y, double* dg, int st = -100) {
+__device__ __forceinline__ void diag_factor(double* S, double* Y, double* dg) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // Y's off-diagonal 16-blocks start at zero (the Z blocks accumulate into them, the
   // upper ones stay zero); waves 1-3 clear them while wave 0 eliminates the first
@@ -274,7 +224,7 @@ __device__ __forceinline__ void diag_factor(double* S, double* Y, double* dg, in
     // the owners publish column j of D and row j of Y to LDS (`bc`, `by`), and every
     // lane reads what it needs in one batch (LDS ops of one wave complete in order,
     // so no barrier), then updates without per-entry selects (no divergent branches).
-    if ((PARTS & 1) && wave == 0) {
+    if (wave == 0) {
       double* Sb = S + o * DP + o;
       double* Yb = Y + o * DP + o;
       double* bc = dg + NB;       // column j of D: 16 slots + 64 dummy slots
@@ -334,7 +284,7 @@ __device__ __forceinline__ void diag_factor(double* S, double* Y, double* dg, in
     const int nC = NBB - 1 - kb, nX = kb;
     doublex4 acc = {0.0, 0.0, 0.0, 0.0};
     int mine = -1;
-    if ((PARTS & 2) && wave < nC + nX) {  // nC + nX = NBB - 1 <= 3: at most one block per wave
+    if (wave < nC + nX) {  // nC + nX = NBB - 1 <= 3: at most one block per wave
       mine = wave;
       if (wave < nC) {
         const int ib = kb + 1 + wave;
@@ -355,7 +305,7 @@ __device__ __forceinline__ void diag_factor(double* S, double* Y, double* dg, in
     if (kb == NBB - 1) break;
     // (3) trailing: S[ib][jb] -= C[ib] C[jb]^T (kb < jb <= ib); Z[ib][jb] -= C[ib] X[kb][jb] (jb <= kb)
     const int nT = (NBB - 1 - kb) * (NBB - kb) / 2, nZ = (NBB - 1 - kb) * (kb + 1);
-    for (int t = wave; (PARTS & 4) && t < nT + nZ; t += 4) {
+    for (int t = wave; t < nT + nZ; t += 4) {
       doublex4 a2 = {0.0, 0.0, 0.0, 0.0};
       double* dst;
       if (t < nT) {
@@ -378,11 +328,20 @@ __device__ __forceinline__ void diag_factor(double* S, double* Y, double* dg, in
   }
 }
 
+// Pivot check of the factored diagonal tile d: info = first global column whose
+// pivot is not positive (+1), one ballot of wave 0 (no serial scan).
+__device__ __forceinline__ void check_pivots(const InvJobDev& J, int d, const double* dg) {
+  if (!J.info || threadIdx.x >= 64) return;
+  const int c = threadIdx.x, g = d * NB + c;
+  const unsigned long long bad = __ballot(c < NB && g < J.n && !(dg[c] > 0.0));
+  if (bad && c == 0) atomicCAS(J.info, 0, d * NB + __ffsll(bad));
+}
+
 // ------------------------------------------------------------------- build R'
 // R'[i][c] = scale*(F[fi][fc] + F[fc][fi])/2 + shift*[i==c], fi = n-1-i, fc = n-1-c.
-// Both source blocks are read row-coalesced into LDS (fp32, P and Q: 64 x 65 floats
+// Both source blocks are read row-coalesced into LDS (fp32, P and Q: NB x (NB+1) floats
 // each), then combined; tile (ti, tj) goes to W (and a copy to LDS `copy` when
-// non-null: the step -1 workgroup factors tile (0,0) straight from it).
+// non-null: the merged build's task 0 factors tile (0,0) straight from it).
 __device__ __forceinline__ void build_tile(const InvJobDev& J, int ti, int tj, float* P, float* Q,
                                            double* copy) {
   const int n = J.n, i0 = ti * NB, c0 = tj * NB;
@@ -447,562 +406,8 @@ __device__ __forceinline__ void emit_zero_block(const InvJobDev& J, int ti, int 
   }
 }
 
-__global__ __launch_bounds__(NTHREADS) void inv_build(InvArgs args) {
-  __shared__ float P[NB * (NB + 1)];  // P[a][b] = F[fi(a)][fc(b)]
-  __shared__ float Q[NB * (NB + 1)];  // Q[b][a] = F[fc(b)][fi(a)]
-  const int j = find_job(args, blockIdx.x);
-  const InvJobDev& J = args.job[j];
-  const int local = blockIdx.x - args.begin[j];
-  if (local == 0 && threadIdx.x == 0 && J.info) *J.info = 0;
-  int ti, tj;
-  tri_decode(local, ti, tj);
-  build_tile(J, ti, tj, P, Q, nullptr);
-}
-
-// Pivot check of the factored diagonal tile d: info = first global column whose
-// pivot is not positive (+1), one ballot of wave 0 (no serial scan).
-__device__ __forceinline__ void check_pivots(const InvJobDev& J, int d, const double* dg) {
-  if (!J.info || threadIdx.x >= 64) return;
-  const int c = threadIdx.x, g = d * NB + c;
-  const unsigned long long bad = __ballot(c < NB && g < J.n && !(dg[c] > 0.0));
-  if (bad && c == 0) atomicCAS(J.info, 0, d * NB + __ffsll(bad));
-}
-
-// acc (gemm64 layout) -> LDS tile
-__device__ __forceinline__ void store_acc_lds(double* S, const doublex4 (&acc)[BPW]) {
-  const int col = threadIdx.x & 15;
-#pragma unroll
-  for (int x = 0; x < BPW; ++x)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) S[(16 * blk_r(x) + acc_row64(v)) * DP + 16 * blk_c(x) + col] = acc[x][v];
-}
-
-// C_i = R'[i][k] X[k][k]^T into Sdst (Xkk already in LDS; Sdst holds R'[i][k] on entry)
-__device__ __forceinline__ void panel_tile_lds(double* Sdst, const double* Xkk) {
-  doublex4 acc[BPW];
-  gemm64<true>(Sdst, Xkk, acc);
-  __syncthreads();  // every wave done reading R'[i][k] before it is overwritten
-  store_acc_lds(Sdst, acc);
-  __syncthreads();
-}
-
-// ------------------------------------------------------------------- step k
-// One launch per elimination step (the panel is folded in: every workgroup forms
-// the panel blocks it needs, C[i][k] = R'[i][k] X[k][k]^T, itself; C is never
-// stored — column k is dead after step k).
-//   k = -1        : factor tile (0,0)                      -> X[0][0]
-//   k <= T-2      : trailing  R'[i][j] -= C_i C_j^T        (i >= j > k)
-//                   the (k+1,k+1) workgroup then factors   -> X[k+1][k+1]
-//                   Z[i][j] -= C_i B,  B = X[k][k] (j = k) or X[k][k] Z[k][j] (j < k)
-//                   row k+1's Z workgroups also store X[k][j] = X[k][k] Z[k][j]
-//                   (final) into W[k][j], dead since step j (Z[k][j] stays intact
-//                   for the other readers of this launch)
-//   k = T-1       : X[k][j] = X[k][k] Z[k][j] -> W[k][j]   (j < k)
-// Final inverse X: diagonal tiles in X, strictly-lower tiles in W (x_tile()).
-// trailing tile (i, j), i >= j > k: R'[i][j] -= C_i C_j^T.  Returns true for the
-// (k+1, k+1) workgroup, which then holds the updated diagonal tile in S0.
-template <bool C = false>
-__device__ __forceinline__ bool step_trailing_ij(const InvJobDev& J, int k, int i, int j, double* S0,
-                                                 double* S1, double* S2) {
-  const bool diag = i == k + 1 && j == k + 1;
-  // the (k+1,k+1) workgroup also prefetches its diagonal tile into the idle S2
-  load_tiles<C>(S0, tile_ptr(J.X, J.Np, k, k), S1, tile_ptr(J.W, J.Np, i, k),
-                (j != i || diag) ? S2 : nullptr, tile_ptr(J.W, J.Np, j != i ? j : i, j != i ? k : i), J.Np);
-  __syncthreads();
-  panel_tile_lds(S1, S0);              // C_i
-  if (j != i) panel_tile_lds(S2, S0);  // C_j
-  doublex4 acc[BPW];
-  gemm64<true>(S1, j != i ? S2 : S1, acc);
-  if (!diag) {
-    store_acc_global<C>(tile_ptr(J.W, J.Np, i, j), J.Np, acc, -1.0, true);
-    return false;
-  }
-  // the updated diagonal tile is consumed right here (never written back)
-  const int col = threadIdx.x & 15;
-#pragma unroll
-  for (int x = 0; x < BPW; ++x)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) S2[(16 * blk_r(x) + acc_row64(v)) * DP + 16 * blk_c(x) + col] -= acc[x][v];
-  __syncthreads();
-  return true;
-}
-
-template <bool C = false>
-__device__ __forceinline__ bool step_trailing(const InvJobDev& J, int k, int local, double* S0,
-                                              double* S1, double* S2) {
-  int a, b;
-  tri_decode(local, a, b);
-  return step_trailing_ij<C>(J, k, k + 1 + a, k + 1 + b, S0, S1, S2);
-}
-
-// Z tile (i, j), i > k >= j: Z[i][j] -= C_i B, B = X[k][k] (j = k) or
-// X[k][k] Z[k][j] (j < k; row k+1's workgroup also stores it as the final X[k][j]).
-template <bool C = false>
-__device__ __forceinline__ void step_z_ij(const InvJobDev& J, int k, int i, int j, double* S0,
-                                          double* S1, double* S2) {
-  load_tiles<C>(S0, tile_ptr(J.X, J.Np, k, k), S1, tile_ptr(J.W, J.Np, i, k), j < k ? S2 : nullptr,
-             tile_ptr(J.X, J.Np, k, j), J.Np);
-  __syncthreads();
-  panel_tile_lds(S1, S0);  // C_i
-  doublex4 acc[BPW];
-  const double* Bm = S0;
-  if (j < k) {
-    gemm64<false>(S0, S2, acc);
-    __syncthreads();
-    store_acc_lds(S2, acc);
-    if (i == k + 1 && J.xw) store_acc_global<C>(tile_ptr(J.W, J.Np, k, j), J.Np, acc, 1.0, false);
-    __syncthreads();
-    Bm = S2;
-  }
-  gemm64<false>(S1, Bm, acc);
-  store_acc_global<C>(tile_ptr(J.X, J.Np, i, j), J.Np, acc, -1.0, true);
-  if (j < k && i == k + 1 && J.fout) emit_out(J, k, j, S2);  // final X[k][j]
-}
-
-template <bool C = false>
-__device__ __forceinline__ void step_z(const InvJobDev& J, int k, int u, double* S0, double* S1,
-                                       double* S2) {
-  step_z_ij<C>(J, k, k + 1 + u / (k + 1), u % (k + 1), S0, S1, S2);
-}
-
-// The second task of a workgroup when it is in the same row i as the first one (tpw = 2
-// takes consecutive tasks): S0 still holds X[k][k] and S1 the panel block C_i, so only
-// the other operand is loaded and only its panel block formed (two of the three tile
-// loads and one of the three panel / update GEMMs of a trailing task saved).
-__device__ __forceinline__ void step_trailing_next(const InvJobDev& J, int k, int i, int j, double* S0,
-                                                   double* S1, double* S2) {
-  if (j != i) {
-    load_tile(S2, tile_ptr(J.W, J.Np, j, k), J.Np);
-    __syncthreads();
-    panel_tile_lds(S2, S0);  // C_j
-  }
-  doublex4 acc[BPW];
-  gemm64<true>(S1, j != i ? S2 : S1, acc);
-  store_acc_global(tile_ptr(J.W, J.Np, i, j), J.Np, acc, -1.0, true);
-}
-
-__device__ __forceinline__ void step_z_next(const InvJobDev& J, int k, int i, int j, double* S0, double* S1,
-                                            double* S2) {
-  doublex4 acc[BPW];
-  const double* Bm = S0;
-  if (j < k) {
-    load_tile(S2, tile_ptr(J.X, J.Np, k, j), J.Np);
-    __syncthreads();
-    gemm64<false>(S0, S2, acc);
-    __syncthreads();
-    store_acc_lds(S2, acc);
-    if (i == k + 1 && J.xw) store_acc_global(tile_ptr(J.W, J.Np, k, j), J.Np, acc, 1.0, false);
-    __syncthreads();
-    Bm = S2;
-  }
-  gemm64<false>(S1, Bm, acc);
-  store_acc_global(tile_ptr(J.X, J.Np, i, j), J.Np, acc, -1.0, true);
-  if (j < k && i == k + 1 && J.fout) emit_out(J, k, j, S2);  // final X[k][j]
-}
-
-// (row, kind) of merged-step task `local` (k >= 0, k + 1 < T): kind 0 trailing, 1 Z
-__device__ __forceinline__ void step_task_row(int T, int k, int local, int& i, int& j, int& kind) {
-  const int nTrail = (T - k - 1) * (T - k) / 2;
-  if (local < nTrail) {
-    int a, b;
-    tri_decode(local, a, b);
-    i = k + 1 + a;
-    j = k + 1 + b;
-    kind = 0;
-  } else {
-    const int u = local - nTrail;
-    i = k + 1 + u / (k + 1);
-    j = u % (k + 1);
-    kind = 1;
-  }
-}
-
-// last row of X (k = T-1): X[k][j] = X[k][k] Z[k][j] -> W[k][j]
-template <bool C = false>
-__device__ __forceinline__ void step_last_row(const InvJobDev& J, int k, int j, double* S0,
-                                              double* S1) {
-  load_tiles<C>(S0, tile_ptr(J.X, J.Np, k, k), S1, tile_ptr(J.X, J.Np, k, j), nullptr, nullptr, J.Np);
-  __syncthreads();
-  doublex4 acc[BPW];
-  gemm64<false>(S0, S1, acc);
-  if (J.xw) store_acc_global<C>(tile_ptr(J.W, J.Np, k, j), J.Np, acc, 1.0, false);
-  if (J.fout) {
-    __syncthreads();  // S1 fully read by the GEMM
-    store_acc_lds(S1, acc);
-    __syncthreads();
-    emit_out(J, k, j, S1);
-  }
-}
-
-// tasks of a job in merged step k (k = -1: the build)
-__device__ __forceinline__ int step_tasks(int T, int k) {
-  if (k < 0) return T * (T + 1) / 2;
-  if (k + 1 < T) return (T - k - 1) * (T - k) / 2 + (T - k - 1) * (k + 1);
-  return k + 1 == T ? k : 0;
-}
-
-// one task of merged step k (task 0 of a job is its critical one: the build's tile
-// (0,0) + its factorisation, or the trailing update + factorisation of (k+1, k+1))
-__device__ __forceinline__ void step_task(const InvArgs& args, int jb, int local, double* S0, double* S1,
-                                          double* S2, double* dg) {
-  const InvJobDev& J = args.job[jb];
-  const int k = args.step, T = J.T;
-  const int nTrail = (T - k - 1) * (T - k) / 2;
-  if (k < 0) {  // build R' (one tile per task); task 0 also factors tile (0,0)
-    int ti, tj;
-    tri_decode(local, ti, tj);
-    if (local == 0 && threadIdx.x == 0 && J.info) *J.info = 0;
-    build_tile(J, ti, tj, reinterpret_cast<float*>(S0), reinterpret_cast<float*>(S1),
-               local == 0 ? S2 : nullptr);
-    if (J.fout && ti != tj) emit_zero_block(J, ti, tj);
-    if (local != 0) return;
-    __syncthreads();
-  } else if (k == T - 1) {
-    step_last_row(J, k, local, S0, S1);
-    if (J.fout && local == 0) emit_out(J, k, k, S0);  // emit_diag: the last diagonal block
-    return;
-  } else if (local >= nTrail) {
-    step_z(J, k, local - nTrail, S0, S1, S2);
-    if (J.fout && local == 1) emit_out(J, k, k, S0);  // emit_diag (S0 = X[k][k], intact)
-    return;
-  } else if (!step_trailing(J, k, local, S0, S1, S2)) {
-    if (J.fout && local == 1) emit_out(J, k, k, S0);  // emit_diag (S0 = X[k][k], intact)
-    return;
-  }
-  // the one diagonal factorisation of this step
-  const int d = k + 1;
-  diag_factor(S2, S1, dg, jb == 0 ? k : -100);
-  check_pivots(J, d, dg);
-  store_tile(tile_ptr(J.X, J.Np, d, d), S1, J.Np);
-  // its L block: emitted here only when no later step has a task to do it (T = 1);
-  // otherwise a non-critical task of step d writes it from its own copy (emit_diag),
-  // off this chain
-  if (J.fout && T == 1) emit_out(J, d, d, S1);
-}
-
-// tpw = 2: workgroup 0 of a job takes the critical task alone, workgroup w >= 1 takes
-// tasks w and w + G - 1 (G workgroups per job), so a step of a big factor fits one
-// dispatch round beside a running SYRK launch (one 29 KB inversion workgroup per CU)
-__device__ __forceinline__ int step_wgs(int count, int tpw) {
-  return (tpw == 2 && count > 1) ? 1 + (count - 1 + 1) / 2 : count;
-}
-
-__global__ __launch_bounds__(NTHREADS) void inv_step(InvArgs args) {
-  // (no s_setprio: priority 3 made the chain win the SIMD's issue arbitration over a
-  // running SYRK launch's waves; with a step of slack priority 0 measured +1-3 % on the
-  // MLP line, the inversion stretching and the SYRK beside it running faster)
-  __shared__ __attribute__((aligned(16))) double S0[NB * DP];
-  __shared__ __attribute__((aligned(16))) double S1[NB * DP];
-  __shared__ __attribute__((aligned(16))) double S2[NB * DP];
-  __shared__ double dg[NB + 352];  // pivots + elimination broadcast buffers
-  const int jb = find_job(args, blockIdx.x);
-  const int wg = blockIdx.x - args.begin[jb];
-  const int count = step_tasks(args.job[jb].T, args.step);
-  // tpw = 2: workgroup w >= 1 takes the consecutive tasks 2w - 1 and 2w, which share
-  // their row (and its panel block) unless a row boundary falls between them
-  const int first = (args.tpw == 2 && wg >= 1) ? 2 * wg - 1 : wg;
-  step_task(args, jb, first, S0, S1, S2, dg);
-  const int second = first + 1;
-  if (args.tpw == 2 && wg >= 1 && second < count) {
-    __syncthreads();  // LDS tiles of the first task are read out
-    const InvJobDev& J = args.job[jb];
-    const int k = args.step, T = J.T;
-    int i0 = -1, j0 = 0, kind0 = -1, i1 = -2, j1 = 0, kind1 = -2;
-    if (k >= 0 && k + 1 < T) {
-      step_task_row(T, k, first, i0, j0, kind0);
-      step_task_row(T, k, second, i1, j1, kind1);
-    }
-    if (i0 == i1 && kind0 == kind1 && !(kind0 == 0 && i0 == k + 1 && j0 == k + 1)) {
-      if (kind1 == 0) step_trailing_next(J, k, i1, j1, S0, S1, S2);
-      else step_z_next(J, k, i1, j1, S0, S1, S2);
-    } else {
-      step_task(args, jb, second, S0, S1, S2, dg);
-    }
-  }
-}
-
-// ------------------------------------------- two-launch step (large factors)
-// For many tiles per edge (T > MERGE_T) the panel is formed ONCE per step
-// (inv_panel, C in place in W and the final X[k][j] in place in X) and
-// inv_update applies it: the merged step's per-workgroup panel recomputation
-// would triple the trailing GEMM work there.  Final X stays entirely in X.
-// update k
-__global__ __launch_bounds__(NTHREADS) void inv_update(InvArgs args) {
-  __shared__ __attribute__((aligned(16))) double A[NB * DP];
-  __shared__ __attribute__((aligned(16))) double B[NB * DP];
-  __shared__ __attribute__((aligned(16))) double Y[NB * DP];
-  __shared__ double dg[NB + 352];  // pivots + elimination broadcast buffers
-  const int jb = find_job(args, blockIdx.x);
-  const InvJobDev& J = args.job[jb];
-  const int k = args.step, T = J.T;
-  const int local = blockIdx.x - args.begin[jb];
-  const int nTrail = (T - k - 1) * (T - k) / 2;
-  if (k < 0 || local < nTrail) {
-    int i = k + 1, j = k + 1;
-    if (k >= 0) {
-      int a, b;
-      tri_decode(local, a, b);
-      i = k + 1 + a;
-      j = k + 1 + b;
-    }
-    const bool factor = (i == k + 1 && j == k + 1);
-    doublex4 acc[BPW];
-    if (k >= 0) {
-      // the factoring workgroup (i == j) prefetches its diagonal tile into Y
-      load_tiles(A, tile_ptr(J.W, J.Np, i, k), B, tile_ptr(J.W, J.Np, j, k), factor ? Y : nullptr,
-                 tile_ptr(J.W, J.Np, i, i), J.Np);
-      __syncthreads();
-      gemm64<true>(A, B, acc);
-    }
-    if (!factor) {
-      store_acc_global(tile_ptr(J.W, J.Np, i, j), J.Np, acc, -1.0, true);
-      return;
-    }
-    // the updated diagonal tile is consumed right here (never written back)
-    __syncthreads();
-    double* D = A;  // diagonal tile
-    double* Yo = Y;  // its factor's inverse
-    if (k >= 0) {
-      D = Y;
-      Yo = A;
-    } else {
-      load_tile(A, tile_ptr(J.W, J.Np, i, i), J.Np);
-      __syncthreads();
-    }
-    if (k >= 0) {
-      const int col = threadIdx.x & 15;
-#pragma unroll
-      for (int x = 0; x < BPW; ++x)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) D[(16 * blk_r(x) + acc_row64(v)) * DP + 16 * blk_c(x) + col] -= acc[x][v];
-      __syncthreads();
-    }
-    diag_factor(D, Yo, dg);
-    check_pivots(J, i, dg);
-    store_tile(tile_ptr(J.X, J.Np, i, i), Yo, J.Np);
-    return;
-  }
-  // Z[i][j] -= C[i][k] X[k][j]   (i > k >= j)
-  const int u = local - nTrail;
-  const int i = k + 1 + u / (k + 1), j = u % (k + 1);
-  load_tiles(A, tile_ptr(J.W, J.Np, i, k), B, tile_ptr(J.X, J.Np, k, j), nullptr, nullptr, J.Np);
-  __syncthreads();
-  doublex4 acc[BPW];
-  gemm64<false>(A, B, acc);
-  store_acc_global(tile_ptr(J.X, J.Np, i, j), J.Np, acc, -1.0, true);
-}
-
-
-// ------------------------------------------------ blocked updates (large factors)
-// The two-launch step re-reads and rewrites the whole trailing matrix (and the Z
-// region) once per panel: for a 4097^2 factor (65 panels of 64) that traffic, not
-// the fp64 MFMA work, sets the time.  With panel blocks of PB panels [k0, ke):
-//   per panel k in the block: inv_panel(k), then inv_inner(k) -- the updates the
-//     block's later panels need: trailing tiles in the block's columns (i >= j,
-//     k < j < ke) and Z tiles in the block's rows (k < i < ke, j <= k); the
-//     (k+1, k+1) workgroup factors it (k + 1 < ke);
-//   then ONE inv_bulk(k0, ke): every other trailing tile (i >= j >= ke) takes all PB
-//     panels at once, R'[i][j] -= sum_k C[i][k] C[j][k]^T, and every Z tile of the
-//     rows below (i >= ke, j < ke) Z[i][j] -= sum_{k >= j} C[i][k] X[k][j]; the
-//     (ke, ke) workgroup factors it.
-// A tile is then read-modified-written once per block instead of once per panel
-// (same arithmetic, summed in another order).
-__device__ __forceinline__ void gemm64_acc_nt(const double* A, const double* B, doublex4 (&acc)[BPW]) {
-#pragma unroll
-  for (int x = 0; x < BPW; ++x)
-    mfma_block<true>(A + 16 * blk_r(x) * DP, DP, B + 16 * blk_c(x) * DP, DP, NB, acc[x]);
-}
-__device__ __forceinline__ void gemm64_acc_nn(const double* A, const double* B, doublex4 (&acc)[BPW]) {
-#pragma unroll
-  for (int x = 0; x < BPW; ++x)
-    mfma_block<false>(A + 16 * blk_r(x) * DP, DP, B + 16 * blk_c(x), DP, NB, acc[x]);
-}
-
-// trailing tile (i, j): R'[i][j] -= sum_{k in [k0, k1)} C[i][k] C[j][k]^T; the
-// (fi, fi) workgroup (fi = i = j) then factors it.
-__device__ __forceinline__ void blk_trailing(const InvJobDev& J, int i, int j, int k0, int k1, bool factor,
-                                             double* A, double* B, double* Y, double* dg) {
-  doublex4 acc[BPW];
-#pragma unroll
-  for (int x = 0; x < BPW; ++x) acc[x] = doublex4{0.0, 0.0, 0.0, 0.0};
-  for (int k = k0; k < k1; ++k) {
-    load_tiles(A, tile_ptr(J.W, J.Np, i, k), B, tile_ptr(J.W, J.Np, j, k),
-               (factor && k == k0) ? Y : nullptr, tile_ptr(J.W, J.Np, i, i), J.Np);
-    __syncthreads();
-    gemm64_acc_nt(A, i == j ? A : B, acc);
-    __syncthreads();
-  }
-  if (!factor) {
-    store_acc_global(tile_ptr(J.W, J.Np, i, j), J.Np, acc, -1.0, true);
-    return;
-  }
-  if (k1 <= k0) {  // (no update: the diagonal tile as it stands)
-    load_tile(Y, tile_ptr(J.W, J.Np, i, i), J.Np);
-    __syncthreads();
-  }
-  const int col = threadIdx.x & 15;
-#pragma unroll
-  for (int x = 0; x < BPW; ++x)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) Y[(16 * blk_r(x) + acc_row64(v)) * DP + 16 * blk_c(x) + col] -= acc[x][v];
-  __syncthreads();
-  diag_factor(Y, A, dg);
-  check_pivots(J, i, dg);
-  store_tile(tile_ptr(J.X, J.Np, i, i), A, J.Np);
-}
-
-// Z tile (i, j): Z[i][j] -= sum_{k in [max(k0, j), k1)} C[i][k] X[k][j]  (X[k][j] is
-// final for j < k, X[k][k] for j = k)
-__device__ __forceinline__ void blk_z(const InvJobDev& J, int i, int j, int k0, int k1, double* A,
-                                      double* B) {
-  doublex4 acc[BPW];
-#pragma unroll
-  for (int x = 0; x < BPW; ++x) acc[x] = doublex4{0.0, 0.0, 0.0, 0.0};
-  for (int k = max(k0, j); k < k1; ++k) {
-    load_tiles(A, tile_ptr(J.W, J.Np, i, k), B, tile_ptr(J.X, J.Np, k, j), nullptr, nullptr, J.Np);
-    __syncthreads();
-    gemm64_acc_nn(A, B, acc);
-    __syncthreads();
-  }
-  store_acc_global(tile_ptr(J.X, J.Np, i, j), J.Np, acc, -1.0, true);
-}
-
-// tasks of a job: inner update of panel k in block [.., ke) / bulk update of block [k0, ke)
-__host__ __device__ inline int inner_trailing(int T, int k, int ke) {
-  int c = 0;
-  for (int j = k + 1; j < ke && j < T; ++j) c += T - j;
-  return c;
-}
-__host__ __device__ inline int inner_tasks(int T, int k, int ke) {
-  if (k >= T) return 0;
-  const int e = ke < T ? ke : T;
-  return inner_trailing(T, k, e) + (e > k + 1 ? (e - k - 1) * (k + 1) : 0);
-}
-__host__ __device__ inline int bulk_tasks(int T, int ke) {
-  return ke >= T ? 0 : (T - ke) * (T - ke + 1) / 2 + (T - ke) * ke;
-}
-// look-ahead parts of a block's bulk update (e2 = end of the next block):
-//   part 1: the next block's columns (trailing tiles i >= j, ke <= j < e2) and Z rows
-//           (ke <= i < e2): what the next block's panels read;
-//   part 2: the rest (trailing j >= e2, Z rows i >= e2), beside the next block's chain.
-__host__ __device__ inline int bulk_next_trailing(int T, int ke, int e2) {
-  int c = 0;
-  for (int j = ke; j < e2; ++j) c += T - j;
-  return c;
-}
-__host__ __device__ inline int bulk_part_tasks(int T, int ke, int e2, int part) {
-  if (ke >= T) return 0;
-  if (part == 0) return bulk_tasks(T, ke);
-  e2 = e2 < T ? e2 : T;
-  if (part == 1) return bulk_next_trailing(T, ke, e2) + (e2 - ke) * ke;
-  return (T - e2) * (T - e2 + 1) / 2 + (T - e2) * ke;
-}
-
-__global__ __launch_bounds__(NTHREADS) void inv_inner(InvArgs args) {
-  __shared__ __attribute__((aligned(16))) double A[NB * DP];
-  __shared__ __attribute__((aligned(16))) double B[NB * DP];
-  __shared__ __attribute__((aligned(16))) double Y[NB * DP];
-  __shared__ double dg[NB + 352];
-  const int jb = find_job(args, blockIdx.x);
-  const InvJobDev& J = args.job[jb];
-  const int k = args.step, T = J.T, ke = min(args.kend, T);
-  int local = blockIdx.x - args.begin[jb];
-  const int nT = inner_trailing(T, k, ke);
-  if (local < nT) {  // column j in (k, ke), row i >= j
-    int j = k + 1;
-    while (local >= T - j) {
-      local -= T - j;
-      ++j;
-    }
-    const int i = j + local;
-    blk_trailing(J, i, j, k, k + 1, i == k + 1 && j == k + 1, A, B, Y, dg);
-    return;
-  }
-  const int u = local - nT;  // row i in (k, ke), column j <= k
-  blk_z(J, k + 1 + u / (k + 1), u % (k + 1), k, k + 1, A, B);
-}
-
-// (two LDS tiles: 2 workgroups per CU; the (ke, ke) tile is stored like the others
-// and factored by inv_diag right after)
-__global__ __launch_bounds__(NTHREADS) void inv_bulk(InvArgs args) {
-  __shared__ __attribute__((aligned(16))) double A[NB * DP];
-  __shared__ __attribute__((aligned(16))) double B[NB * DP];
-  const int jb = find_job(args, blockIdx.x);
-  const InvJobDev& J = args.job[jb];
-  const int k0 = args.step, T = J.T, ke = min(args.kend, T);
-  int local = blockIdx.x - args.begin[jb];
-  if (args.part == 1) {  // the next block's columns and Z rows
-    const int e2 = min(args.ksplit, T);
-    const int nT = bulk_next_trailing(T, ke, e2);
-    if (local < nT) {
-      int j = ke;
-      while (local >= T - j) {
-        local -= T - j;
-        ++j;
-      }
-      blk_trailing(J, j + local, j, k0, ke, false, A, B, nullptr, nullptr);
-      return;
-    }
-    const int u = local - nT;
-    blk_z(J, ke + u / ke, u % ke, k0, ke, A, B);
-    return;
-  }
-  const int r0 = args.part == 2 ? min(args.ksplit, T) : ke;  // first row / column
-  const int nT = (T - r0) * (T - r0 + 1) / 2;
-  if (local < nT) {
-    int a, b;
-    tri_decode(local, a, b);
-    blk_trailing(J, r0 + a, r0 + b, k0, ke, false, A, B, nullptr, nullptr);
-    return;
-  }
-  const int u = local - nT;
-  blk_z(J, r0 + u / ke, u % ke, k0, ke, A, B);
-}
-
-// factor the diagonal tile (d, d) = (args.step, args.step) of every job: X[d][d]
-__global__ __launch_bounds__(NTHREADS) void inv_diag(InvArgs args) {
-  __shared__ __attribute__((aligned(16))) double A[NB * DP];
-  __shared__ __attribute__((aligned(16))) double Y[NB * DP];
-  __shared__ double dg[NB + 352];
-  const InvJobDev& J = args.job[find_job(args, blockIdx.x)];
-  const int d = args.step;
-  load_tile(Y, tile_ptr(J.W, J.Np, d, d), J.Np);
-  __syncthreads();
-  diag_factor(Y, A, dg);
-  check_pivots(J, d, dg);
-  store_tile(tile_ptr(J.X, J.Np, d, d), A, J.Np);
-}
-
-// -------------------------------------------------------------------- panel k
-__global__ __launch_bounds__(NTHREADS) void inv_panel(InvArgs args) {
-  __shared__ __attribute__((aligned(16))) double A[NB * DP];
-  __shared__ __attribute__((aligned(16))) double Xk[NB * DP];
-  const int jb = find_job(args, blockIdx.x);
-  const InvJobDev& J = args.job[jb];
-  const int k = args.step, T = J.T;
-  const int local = blockIdx.x - args.begin[jb];
-  const int nC = T - k - 1;
-  doublex4 acc[BPW];
-  if (local < nC) {  // C[i][k] = R'[i][k] X[k][k]^T
-    const int i = k + 1 + local;
-    double* t = tile_ptr(J.W, J.Np, i, k);
-    load_tiles(Xk, tile_ptr(J.X, J.Np, k, k), A, t, nullptr, nullptr, J.Np);
-    __syncthreads();
-    gemm64<true>(A, Xk, acc);
-    store_acc_global(t, J.Np, acc, 1.0, false);
-  } else {           // X[k][j] = X[k][k] Z[k][j]
-    const int j = local - nC;
-    double* t = tile_ptr(J.X, J.Np, k, j);
-    load_tiles(Xk, tile_ptr(J.X, J.Np, k, k), A, t, nullptr, nullptr, J.Np);
-    __syncthreads();
-    gemm64<false>(Xk, A, acc);
-    store_acc_global(t, J.Np, acc, 1.0, false);
-  }
-}
-
-
-// final inverse X tile (a >= b): with the merged step the strictly-lower tiles live
-// in W (see inv_step), with the two-launch step everything is in X
+// final inverse X tile (a >= b): the merged path leaves the strictly-lower tiles in W
+// (xw, see inv_step), the blocked path everything in X
 __device__ __forceinline__ const double* x_tile(const InvJobDev& J, int a, int b) {
   return tile_ptr(a > b && J.xw ? J.W : J.X, J.Np, a, b);
 }
@@ -1058,288 +463,23 @@ __global__ __launch_bounds__(NTHREADS) void inv_out(InvArgs args) {
 }
 
 // ---------------------------------------------------------------- host side
-// staged outputs of the graph-replayed step chain: L (n x n fp32) and the verdict
+// A job's workspace region: W, X, Tm (Np x Np doubles each), then the staging area of
+// the graph-replayed merged chain: L (n x n fp32) and the verdict.
 static size_t stage_bytes(int64_t n) { return align_up((size_t)(n * n) * sizeof(float) + 256, 256); }
 
-static size_t job_ws(const kfac_invert_job& j) {
+size_t job_ws(const kfac_invert_job& j) {
   const int64_t T = cdiv(j.n, NB), Np = T * NB;
   return 3 * align_up((size_t)(Np * Np) * sizeof(double), 256) + stage_bytes(j.n);
 }
 
-// ------------------------------------------------------- graph-replayed step chain
-// The latency-bound inversion is ~25 dependent step launches; issuing them costs
-// the host more than the GPU spends per step.  With KFAC_INV_GRAPH (default on) the
-// steps are one cached hipGraph per (stream, job set): the launches' arguments must
-// then not change between calls, so every step writes L and the verdict to staging
-// buffers in the workspace, and one inv_copy_out launch after the graph copies them
-// to the caller's outputs.  The graph is rebuilt when anything else in the
-// arguments changes (factor pointers, sizes, damping, workspace).
-struct UnstageJob {
-  const float* src;
-  float* dst;
-  int64_t ldo;
-  const int* isrc;
-  int* idst;
-  int n;
-};
-struct UnstageArgs {
-  int njobs;
-  int begin[IMAXJ + 1];  // blocks per job: ceil(n / 4) rows-of-4
-  UnstageJob job[IMAXJ];
-};
-
-__global__ __launch_bounds__(NTHREADS) void inv_copy_out(UnstageArgs a) {
-  int j = 0;
-  while (j + 1 < a.njobs && (int)blockIdx.x >= a.begin[j + 1]) ++j;
-  const UnstageJob& U = a.job[j];
-  const int r0 = ((int)blockIdx.x - a.begin[j]) * 4;
-  if (r0 == 0 && threadIdx.x == 0 && U.idst) *U.idst = *U.isrc;
-  for (int r = r0; r < r0 + 4 && r < U.n; ++r)
-    for (int c = threadIdx.x; c < U.n; c += NTHREADS) U.dst[(int64_t)r * U.ldo + c] = U.src[(int64_t)r * U.n + c];
-}
-
-static bool graph_enabled() { return knobs().inv_graph != 0; }
-
-// A cached chain is keyed by its SHAPE (stream, step count, per-job sizes / kinds,
-// launch knobs): a call whose arguments differ only in values -- damping (scale,
-// shift), factor / output / workspace pointers -- updates the instantiated graph's
-// kernel nodes in place (hipGraphExecKernelNodeSetParams: launches already queued
-// keep the arguments they were queued with) instead of building a new graph, so a
-// damping schedule or a grid over (add, multiply) replays one graph.  An evicted
-// entry waits for its last replay (an event recorded after it) before its graph is
-// destroyed.
-struct GraphEntry {
-  hipStream_t stream = nullptr;
-  int tmax = 0;
-  int njobs = 0, tpw = 0;
-  int n[IMAXJ] = {}, kind[IMAXJ] = {};
-  InvArgs args{};    // phase-1 arguments the nodes hold now (step / begin cleared)
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  hipEvent_t last = nullptr;  // recorded after the latest replay
-  std::vector<hipGraphNode_t> nodes;
-  std::vector<int> node_step;
-  unsigned long long used = 0;
-};
-static std::mutex g_graph_mu;
-static GraphEntry g_graphs[8];
-static unsigned long long g_graph_tick = 0;
-
-static bool same_shape(const GraphEntry& e, const InvArgs& a, int Tmax, hipStream_t s) {
-  if (!e.exec || e.stream != s || e.tmax != Tmax || e.njobs != a.njobs || e.tpw != a.tpw)
-    return false;
-  for (int j = 0; j < a.njobs; ++j)
-    if (e.n[j] != a.job[j].n || e.kind[j] != a.job[j].kind) return false;
-  return true;
-}
-
-// the arguments of step k's launch: `a` with step k and its job offsets; 0 = no tasks
-static int step_args(InvArgs& a, int k) {
-  a.step = k;
-  int total = 0;
-  for (int j = 0; j < a.njobs; ++j) {
-    a.begin[j] = total;
-    const int T = a.job[j].T;
-    int c;
-    if (k + 1 < T) c = (T - k - 1) * (T - k) / 2 + (T - k - 1) * (k + 1);
-    else c = k + 1 == T ? k : 0;
-    total += (a.tpw == 2 && c > 1) ? 1 + (c - 1 + 1) / 2 : c;
-  }
-  a.begin[a.njobs] = total;
-  return total;
-}
-
-static hipKernelNodeParams step_node(InvArgs& a, void** params, int total) {
-  hipKernelNodeParams p{};
-  params[0] = &a;
-  p.func = reinterpret_cast<void*>(inv_step);
-  p.gridDim = dim3(total);
-  p.blockDim = dim3(NTHREADS);
-  p.sharedMemBytes = 0;
-  p.kernelParams = params;
-  p.extra = nullptr;
-  return p;
-}
-
-static void drop_entry(GraphEntry& e) {
-  if (e.last) {
-    (void)hipEventSynchronize(e.last);  // its last replay has finished
-    (void)hipEventDestroy(e.last);
-  }
-  if (e.exec) (void)hipGraphExecDestroy(e.exec);
-  if (e.graph) (void)hipGraphDestroy(e.graph);
-  e = GraphEntry{};
-}
-
-// every cached graph: wait for its last replay, then destroy it (kfac_release)
-void release_graphs() {
-  std::lock_guard<std::mutex> lk(g_graph_mu);
-  for (GraphEntry& e : g_graphs) drop_entry(e);
-}
-
-// phase 1 of the merged path (steps 0 .. Tmax-1) as a replay of a cached graph
-static int launch_steps_graph(const InvArgs& args, int Tmax, hipStream_t s) {
-  InvArgs key;
-  memcpy(&key, &args, sizeof(InvArgs));
-  key.step = 0;
-  for (int j = 0; j <= IMAXJ; ++j) key.begin[j] = 0;
-  std::lock_guard<std::mutex> lk(g_graph_mu);
-  GraphEntry* hit = nullptr;
-  GraphEntry* lru = nullptr;
-  for (GraphEntry& e : g_graphs) {
-    if (same_shape(e, args, Tmax, s)) {
-      // new values go into the nodes only once the entry's last replay has finished:
-      // HIP gives no guarantee that a replay still queued keeps the arguments it was
-      // launched with, so a busy entry is left alone (another one is used or built)
-      if (memcmp(&e.args, &key, sizeof(InvArgs)) == 0 || hipEventQuery(e.last) == hipSuccess) {
-        hit = &e;
-        break;
-      }
-      continue;
-    }
-    if (!lru || e.used < lru->used) lru = &e;
-  }
-  if (!hit && !lru) {  // every entry is a busy one of this shape: the oldest, once idle
-    lru = &g_graphs[0];
-    for (GraphEntry& e : g_graphs)
-      if (e.used < lru->used) lru = &e;
-  }
-  if (hit && memcmp(&hit->args, &key, sizeof(InvArgs)) != 0) {
-    // same shape, other values: new arguments into the existing nodes
-    for (size_t q = 0; q < hit->nodes.size(); ++q) {
-      InvArgs a = args;
-      const int total = step_args(a, hit->node_step[q]);
-      void* params[1];
-      hipKernelNodeParams p = step_node(a, params, total);
-      if (hipGraphExecKernelNodeSetParams(hit->exec, hit->nodes[q], &p) != hipSuccess) {
-        drop_entry(*hit);
-        hit = nullptr;
-        break;
-      }
-    }
-    if (hit) hit->args = key;
-  }
-  if (!hit) {
-    GraphEntry& e = *lru;
-    drop_entry(e);
-    if (hipGraphCreate(&e.graph, 0) != hipSuccess) return KFAC_ELAUNCH;
-    hipGraphNode_t prev = nullptr;
-    for (int k = 0; k < Tmax; ++k) {
-      InvArgs a = args;
-      const int total = step_args(a, k);
-      if (total == 0) continue;
-      void* params[1];
-      hipKernelNodeParams p = step_node(a, params, total);
-      hipGraphNode_t node;
-      if (hipGraphAddKernelNode(&node, e.graph, prev ? &prev : nullptr, prev ? 1 : 0, &p) != hipSuccess) {
-        drop_entry(e);
-        return KFAC_ELAUNCH;
-      }
-      e.nodes.push_back(node);
-      e.node_step.push_back(k);
-      prev = node;
-    }
-    if (hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0) != hipSuccess ||
-        hipEventCreateWithFlags(&e.last, hipEventDisableTiming) != hipSuccess) {
-      drop_entry(e);
-      return KFAC_ELAUNCH;
-    }
-    e.stream = s;
-    e.tmax = Tmax;
-    e.njobs = args.njobs;
-    e.tpw = args.tpw;
-    for (int j = 0; j < args.njobs; ++j) {
-      e.n[j] = args.job[j].n;
-      e.kind[j] = args.job[j].kind;
-    }
-    e.args = key;
-    hit = &e;
-  }
-  hit->used = ++g_graph_tick;
-  if (hipGraphLaunch(hit->exec, s) != hipSuccess) return KFAC_ELAUNCH;
-  return hipEventRecord(hit->last, s) == hipSuccess ? KFAC_OK : KFAC_ELAUNCH;
-}
-
-// Look-ahead of the blocked path (KFAC_INV_LOOKAHEAD, default 1): a block's bulk
-// update is split into the part the next block's panels read (on the caller's stream)
-// and the rest, which runs on a helper stream beside the next block's panel / inner
-// chain (the latency-bound part of the step).  One helper stream and two ordering
-// events per caller stream.
-struct LookAhead {
-  hipStream_t s = nullptr;  // the caller's stream
-  hipStream_t s2 = nullptr;
-  hipEvent_t chain = nullptr, rest = nullptr;
-};
-static std::mutex g_la_mu;
-static std::vector<LookAhead> g_la;
-
-constexpr size_t LA_MAX = 64;  // caller streams with a helper (stable addresses: reserved once)
-
-static const LookAhead* look_ahead(hipStream_t s) {
-  if (!knobs().inv_lookahead) return nullptr;
-  std::lock_guard<std::mutex> lk(g_la_mu);
-  for (const LookAhead& l : g_la)
-    if (l.s == s) return &l;
-  // past LA_MAX caller streams the blocked path runs without the helper (nothing created)
-  g_la.reserve(LA_MAX);
-  if (g_la.size() == LA_MAX) return nullptr;
-  LookAhead l;
-  l.s = s;
-  if (hipStreamCreateWithFlags(&l.s2, hipStreamNonBlocking) != hipSuccess) return nullptr;
-  if (hipEventCreateWithFlags(&l.chain, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&l.rest, hipEventDisableTiming) != hipSuccess) {
-    if (l.chain) (void)hipEventDestroy(l.chain);
-    (void)hipStreamDestroy(l.s2);
-    return nullptr;
-  }
-  g_la.push_back(l);
-  return &g_la.back();
-}
-
-void release_look_ahead() {
-  std::lock_guard<std::mutex> lk(g_la_mu);
-  for (LookAhead& l : g_la) {
-    (void)hipStreamSynchronize(l.s2);
-    (void)hipEventDestroy(l.chain);
-    (void)hipEventDestroy(l.rest);
-    (void)hipStreamDestroy(l.s2);
-  }
-  g_la.clear();
-}
-
-// panels per block of the two-launch path's updates: 6 with the look-ahead and 16-byte
-// loads (4097^2: 6.18 vs 6.25 ms at 4, 6.31 at 8; DESIGN.md 3.3)
-constexpr int PANEL_BLOCK = 6;
-static int panel_block() { return PANEL_BLOCK; }
-
-template <typename Count>
-static int launch(void (*kern)(InvArgs), InvArgs& args, Count count, hipStream_t s) {
-  int total = 0;
-  for (int j = 0; j < args.njobs; ++j) {
-    args.begin[j] = total;
-    total += count(args.job[j]);
-  }
-  args.begin[args.njobs] = total;
-  if (total == 0) return KFAC_OK;
-  hipLaunchKernelGGL(kern, dim3(total), dim3(NTHREADS), 0, s, args);
-  KFAC_CHECK_LAUNCH();
-  return KFAC_OK;
-}
-
-// Phase 0 = the launch that reads F (merged: step -1, which builds R' and factors
-// tile (0,0); two-launch path: inv_build); phase 1 = everything after it.
-static int invert_group(const kfac_invert_job* jobs, int njobs, char* ws, int32_t* info,
-                        hipStream_t s, int phase) {
-  InvArgs args;
+// InvArgs of a group of jobs whose regions start at `ws`; returns the most tiles per
+// edge.  tpw / xw / fout and the per-launch fields are the path's to set.  `stage`
+// (may be null) receives each job's staging area.
+static int fill_args(InvArgs& args, const kfac_invert_job* jobs, int njobs, char* ws, int32_t* info,
+                     float** stage) {
   memset(&args, 0, sizeof(args));  // (padding too: the graph cache compares the bytes)
   args.njobs = njobs;
-  // 2 tasks per workgroup for 32-tiles: +1.2 % on the MLP bench (3 A/B pairs), the
-  // early steps of a 785 factor fit one round
-  args.tpw = NB == 32 ? 2 : 1;
   int Tmax = 0;
-  bool any_inverse = false;
-  float* stage_out[IMAXJ];
-  int* stage_info[IMAXJ];
   for (int i = 0; i < njobs; ++i) {
     const kfac_invert_job& jb = jobs[i];
     InvJobDev& d = args.job[i];
@@ -1358,131 +498,33 @@ static int invert_group(const kfac_invert_job* jobs, int njobs, char* ws, int32_
     d.W = reinterpret_cast<double*>(ws);
     d.X = reinterpret_cast<double*>(ws + mat);
     d.Tm = reinterpret_cast<double*>(ws + 2 * mat);
-    stage_out[i] = reinterpret_cast<float*>(ws + 3 * mat);
-    stage_info[i] = reinterpret_cast<int*>(stage_out[i]) + (size_t)jb.n * jb.n;
-    ws += 3 * mat + stage_bytes(jb.n);
+    if (stage) stage[i] = reinterpret_cast<float*>(ws + 3 * mat);
+    ws += job_ws(jb);
     Tmax = std::max(Tmax, d.T);
-    any_inverse |= jb.out_kind == KFAC_OUT_INVERSE;
   }
-  // latency-bound (few tiles per edge): one launch per step; else panel once per step
-  const bool merged = Tmax <= MERGE_T;
-  bool all_fused = merged;
-  for (int i = 0; i < njobs; ++i) {
-    args.job[i].xw = merged;
-    args.job[i].fout = merged && args.job[i].kind == KFAC_OUT_INV_CHOL;
-    all_fused &= args.job[i].fout != 0;
-  }
-  int rc;
-  // graph-replayed steps (merged path, inverse-Cholesky outputs): outputs staged
-  if (merged && all_fused && graph_enabled()) {
-    UnstageArgs ua{};
-    ua.njobs = njobs;
-    int blocks = 0;
-    for (int i = 0; i < njobs; ++i) {
-      InvJobDev& d = args.job[i];
-      ua.job[i] = UnstageJob{stage_out[i], d.out, d.ldo, stage_info[i], d.info, d.n};
-      ua.begin[i] = blocks;
-      blocks += (d.n + 3) / 4;
-      d.out = stage_out[i];
-      d.ldo = d.n;
-      d.info = stage_info[i];
-    }
-    ua.begin[njobs] = blocks;
-    if (!phase) {
-      args.step = -1;
-      const int tpw = args.tpw;
-      return launch(inv_step, args, [tpw](const InvJobDev& d) {
-        const int c = d.T * (d.T + 1) / 2;  // build every tile; task 0 factors (0,0)
-        return (tpw == 2 && c > 1) ? 1 + (c - 1 + 1) / 2 : c;
-      }, s);
-    }
-    rc = launch_steps_graph(args, Tmax, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(inv_copy_out, dim3(blocks), dim3(NTHREADS), 0, s, ua);
-    KFAC_CHECK_LAUNCH();
-    return KFAC_OK;
-  }
-  // info is zeroed by the first launch (workgroup 0 of each job)
-  if (merged) {
-    for (int k = phase ? 0 : -1; k < (phase ? Tmax : 0); ++k) {
-      args.step = k;
-      const int tpw = args.tpw;
-      rc = launch(inv_step, args, [k, tpw](const InvJobDev& d) {
-        int c;
-        if (k < 0) c = d.T * (d.T + 1) / 2;  // build every tile; task 0 factors (0,0)
-        else if (k + 1 < d.T) c = (d.T - k - 1) * (d.T - k) / 2 + (d.T - k - 1) * (k + 1);
-        else c = k + 1 == d.T ? k : 0;  // last row of X
-        return (tpw == 2 && c > 1) ? 1 + (c - 1 + 1) / 2 : c;
-      }, s);
-      if (rc) return rc;
-    }
-    if (!phase) return KFAC_OK;
-  } else {
-    if (!phase) return launch(inv_build, args, [](const InvJobDev& d) { return d.T * (d.T + 1) / 2; }, s);
-    args.step = -1;
-    rc = launch(inv_update, args, [](const InvJobDev&) { return 1; }, s);
-    if (rc) return rc;
-    const int pb = panel_block();
-    if (pb <= 1) {
-      for (int k = 0; k < Tmax; ++k) {
-        args.step = k;
-        rc = launch(inv_panel, args, [k](const InvJobDev& d) { return k < d.T ? d.T - 1 : 0; }, s);
-        if (rc) return rc;
-        rc = launch(inv_update, args, [k](const InvJobDev& d) {
-          return k + 1 < d.T ? (d.T - k - 1) * (d.T - k) / 2 + (d.T - k - 1) * (k + 1) : 0;
-        }, s);
-        if (rc) return rc;
-      }
-    } else {
-      const LookAhead* la = look_ahead(s);
-      bool rest_pending = false;
-      for (int k0 = 0; k0 < Tmax; k0 += pb) {
-        const int ke = k0 + pb, e2 = ke + pb;
-        args.kend = ke;
-        for (int k = k0; k < ke && k < Tmax; ++k) {
-          args.step = k;
-          rc = launch(inv_panel, args, [k](const InvJobDev& d) { return k < d.T ? d.T - 1 : 0; }, s);
-          if (rc) return rc;
-          rc = launch(inv_inner, args, [k, ke](const InvJobDev& d) { return inner_tasks(d.T, k, ke); }, s);
-          if (rc) return rc;
-        }
-        args.step = k0;
-        if (la && ke < Tmax) {
-          // the chain of this block is done: the rest of its bulk may start (helper)
-          if (hipEventRecord(la->chain, s) != hipSuccess) return KFAC_ELAUNCH;
-          // the previous block's rest wrote the columns the next part updates
-          if (rest_pending && hipStreamWaitEvent(s, la->rest, 0) != hipSuccess) return KFAC_ELAUNCH;
-          args.ksplit = e2;
-          args.part = 1;
-          rc = launch(inv_bulk, args, [ke, e2](const InvJobDev& d) { return bulk_part_tasks(d.T, ke, e2, 1); }, s);
-          if (rc) return rc;
-          if (hipStreamWaitEvent(la->s2, la->chain, 0) != hipSuccess) return KFAC_ELAUNCH;
-          args.part = 2;
-          rc = launch(inv_bulk, args, [ke, e2](const InvJobDev& d) { return bulk_part_tasks(d.T, ke, e2, 2); },
-                      la->s2);
-          if (rc) return rc;
-          if (hipEventRecord(la->rest, la->s2) != hipSuccess) return KFAC_ELAUNCH;
-          rest_pending = true;
-          args.part = 0;
-        } else {
-          if (rest_pending && hipStreamWaitEvent(s, la->rest, 0) != hipSuccess) return KFAC_ELAUNCH;
-          rest_pending = false;
-          rc = launch(inv_bulk, args, [ke](const InvJobDev& d) { return bulk_tasks(d.T, ke); }, s);
-          if (rc) return rc;
-        }
-        args.step = ke;
-        rc = launch(inv_diag, args, [ke](const InvJobDev& d) { return ke < d.T ? 1 : 0; }, s);
-        if (rc) return rc;
-      }
-      if (rest_pending && hipStreamWaitEvent(s, la->rest, 0) != hipSuccess) return KFAC_ELAUNCH;
-    }
-  }
-  if (any_inverse) {
-    rc = launch(inv_xtx, args,
-                [](const InvJobDev& d) { return d.kind == KFAC_OUT_INVERSE ? d.T * (d.T + 1) / 2 : 0; }, s);
-    if (rc) return rc;
-  }
-  if (all_fused) return KFAC_OK;  // the steps already wrote every L
-  return launch(inv_out, args, [](const InvJobDev& d) { return d.fout ? 0 : d.T * d.T; }, s);
+  return Tmax;
 }
 
+// one launch over every job's tasks (count(job) workgroups each; none: no launch)
+template <typename Count>
+static int launch(void (*kern)(InvArgs), InvArgs& args, Count count, hipStream_t s) {
+  int total = 0;
+  for (int j = 0; j < args.njobs; ++j) {
+    args.begin[j] = total;
+    total += count(args.job[j]);
+  }
+  args.begin[args.njobs] = total;
+  if (total == 0) return KFAC_OK;
+  hipLaunchKernelGGL(kern, dim3(total), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}
+
+// After the elimination: Y = X^T X for the full-inverse jobs, then the output pass of
+// every job whose L the steps did not already write (fout).
+static int launch_outputs(InvArgs& args, hipStream_t s) {
+  const int rc = launch(inv_xtx, args,
+                        [](const InvJobDev& d) { return d.kind == KFAC_OUT_INVERSE ? d.T * (d.T + 1) / 2 : 0; }, s);
+  if (rc) return rc;
+  return launch(inv_out, args, [](const InvJobDev& d) { return d.fout ? 0 : d.T * d.T; }, s);
+}

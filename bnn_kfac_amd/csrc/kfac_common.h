@@ -19,6 +19,7 @@ constexpr int BK = 32;          // rows of k staged per pipeline step
 constexpr int LDP = TILE + 1;   // padded LDS row pitch (floats): column writes conflict-free
 constexpr int NTHREADS = 256;   // 4 waves
 constexpr int PANEL = BK * (TILE + 4); // floats per staged panel (max pitch)
+constexpr int IMAXJ = 8;        // factors per grouped launch of the fp64 inversion
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 

@@ -59,6 +59,77 @@ def test_grouped_invert_and_inverse_kind(hip_device):
         np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=1e-4, atol=1e-7 * np.abs(ref).max())
 
 
+def _invert_group(mats, kinds, dev):
+    """One grouped call (scale 3, shift 0.5) on `dev`; returns (outs, info), synchronised."""
+    from bnn_kfac_amd import _native as N
+    jobs, outs = [], []
+    for F, kind in zip(mats, kinds):
+        Ft = _t(F, dev)
+        outs.append(torch.full_like(Ft, float("nan")))
+        jobs.append(N.invert_job(Ft, outs[-1], 3.0, 0.5, kind))
+    info = N.invert(jobs, dev)
+    torch.cuda.synchronize()
+    return outs, info.cpu()
+
+
+def _check_group(mats, kinds, outs, info):
+    from bnn_kfac_amd import _native as N
+    assert not info.any()
+    for F, kind, out in zip(mats, kinds, outs):
+        R = O.damped_factor(F, 0.25, 9.0)
+        ref = np.linalg.inv(R) if kind == N.OUT_INVERSE else np.linalg.cholesky(np.linalg.inv(R))
+        got = out.cpu().numpy()
+        np.testing.assert_allclose(got, ref, rtol=1e-4, atol=1e-7 * np.abs(ref).max())
+        if kind == N.OUT_INV_CHOL:
+            assert np.all(np.triu(got, 1) == 0)
+
+
+@pytest.fixture(scope="module")
+def blocked_group():
+    """1537 is the smallest size on 64-tiles (T = 25: five panel blocks, four with
+    look-ahead); the 70 and 200 jobs run out of tasks in the early blocks."""
+    from bnn_kfac_amd import _native as N
+    rng = np.random.default_rng(17)
+    return ([_spd(n, rng, 1e3) for n in (1537, 70, 200)],
+            [N.OUT_INV_CHOL, N.OUT_INVERSE, N.OUT_INVERSE])
+
+
+def test_blocked_grouped_both_kinds(hip_device, blocked_group):
+    mats, kinds = blocked_group
+    outs, info = _invert_group(mats, kinds, hip_device)
+    _check_group(mats, kinds, outs, info)
+
+
+def test_blocked_lookahead_bit_exact(hip_device, blocked_group):
+    """Each tile sums the same panels in the same order whichever part of the bulk
+    update owns it: the helper-stream split changes no bit."""
+    from bnn_kfac_amd import _native as N
+    mats, kinds = blocked_group
+    before = N.get_knob("KFAC_INV_LOOKAHEAD")
+    got = {}
+    try:
+        for la in (0, 1):
+            N.set_knob("KFAC_INV_LOOKAHEAD", la)
+            outs, info = _invert_group(mats, kinds, hip_device)
+            assert not info.any()
+            got[la] = outs
+    finally:
+        N.set_knob("KFAC_INV_LOOKAHEAD", before)
+    for a, b in zip(got[0], got[1]):
+        assert torch.equal(a, b)
+
+
+def test_merged_upper_limit_inverse_kind(hip_device):
+    """n = 1536 is the largest size on 32-tiles (T = 48); a full-inverse job in the group
+    keeps the steps off the graph replay and the output on inv_xtx / inv_out."""
+    from bnn_kfac_amd import _native as N
+    rng = np.random.default_rng(19)
+    mats = [_spd(n, rng, 1e3) for n in (1536, 33)]
+    kinds = [N.OUT_INVERSE, N.OUT_INV_CHOL]
+    outs, info = _invert_group(mats, kinds, hip_device)
+    _check_group(mats, kinds, outs, info)
+
+
 def test_kfac_invert_small_golden(hip_device):
     from bnn_kfac_amd.curvatures import KFAC
     g = golden("g1_small_linear.npz")

@@ -1,4 +1,4 @@
-"""GPU: the inversion's hipGraph cache (invert_tiles.inc launch_steps_graph) gives the
+"""GPU: the inversion's hipGraph cache (invert_merged.hip launch_steps_graph) gives the
 same bits as the uncached per-step launches (KFAC_INV_GRAPH=0) of
 models/curvatures.py:381-396's L = cholesky(inverse(sqrt(s)F + sqrt(n)I)):
 

@@ -3,8 +3,8 @@
 
 * the SYRK of a 4096-wide layer (A 4097^2 with the ones column, G 4096^2) through
   KFAC.update (curvatures.py:345-363), rtol 1e-5 of the factor's scale;
-* KFAC.invert at n = 4097 / 4096 (curvatures.py:381-398): the 64-tile two-launch
-  path (inv_panel + inv_update, T = 65 tiles per edge), atol 1e-4 of max|L|
+* KFAC.invert at n = 4097 / 4096 (curvatures.py:381-398): the 64-tile blocked
+  path (inv_panel + inv_inner / inv_bulk, T = 65 tiles per edge), atol 1e-4 of max|L|
   (the north-star figure) vs cholesky(inv(R)) in fp64 on the device's own factor;
 * eigenvalues at n = 4097 (utilities.py:120-141) vs LAPACK eigvalsh in fp64.
 """
