@@ -72,6 +72,12 @@ class CovJob(ctypes.Structure):
                 ("lower2", c_i32)]
 
 
+class CovOuterJob(ctypes.Structure):
+    _fields_ = [("a", c_vp), ("lda", c_i64), ("cols", c_i32), ("has_ones", c_i32), ("D", c_vp),
+                ("ldD", c_i64), ("nG", c_i32), ("reserved", c_i32), ("K1", c_vp), ("ld1", c_i64),
+                ("K2", c_vp), ("ld2", c_i64), ("lower1", c_i32), ("lower2", c_i32)]
+
+
 class SampleJob(ctypes.Structure):
     _fields_ = [("LA", c_vp), ("ldA", c_i64), ("LG", c_vp), ("ldG", c_i64), ("Z", c_vp),
                 ("nA", c_i32), ("nG", c_i32), ("W", c_vp), ("ldW", c_i64), ("bias", c_vp),
@@ -128,6 +134,10 @@ SIGNATURES = {
                                                         ctypes.c_int]),
     "kfac_kron_cov": (ctypes.c_int, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64, ctypes.c_int,
                                      ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_kron_cov_outer_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovOuterJob), ctypes.c_int,
+                                                              c_i64, ctypes.c_int]),
+    "kfac_kron_cov_outer": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                           ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "kfac_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SampleJob), ctypes.c_int]),
     "kfac_sample": (ctypes.c_int, [ctypes.POINTER(SampleJob), ctypes.c_int, ctypes.c_int, c_vp,
                                    ctypes.c_size_t, c_vp]),
@@ -453,6 +463,20 @@ def kron_cov(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False
     ws = workspace.get(out.device, need)
     check(L.kfac_kron_cov(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
                           stream_handle(out.device)), "kfac_kron_cov")
+
+
+def kron_cov_outer_workspace_bytes(jobs, nb: int, nc: int) -> int:
+    return lib().kfac_kron_cov_outer_workspace_bytes(as_array(CovOuterJob, jobs), len(jobs), nb, nc)
+
+
+def kron_cov_outer(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_kron_cov_outer: out (nb, nc, nc) (+)= sum_j s_j V_j V_j^T, <= 8 jobs per call."""
+    L = lib()
+    arr = as_array(CovOuterJob, jobs)
+    need = L.kfac_kron_cov_outer_workspace_bytes(arr, len(jobs), nb, nc)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_kron_cov_outer(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
+                                stream_handle(out.device)), "kfac_kron_cov_outer")
 
 
 def sample(jobs, device: torch.device, accumulate: bool) -> None:

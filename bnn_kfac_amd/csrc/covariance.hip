@@ -20,13 +20,10 @@
 // a0 the K-range [a0, nA)), and run in plain block order: the round-robin dispatch gives
 // every XCD the same mix.  Contiguous per-XCD ranges (xcd_task) put the long a-tiles on
 // XCD 0 and the short ones on XCD 7 and measured 1.5x slower; K1 fits any one L2.
-#include "kfac_common.h"
+#include "covariance_common.h"
 
 namespace kfac {
 
-constexpr int CMAXJ = 8;
-constexpr int CMAXC = 32;           // nc: one 32x32 MFMA quadrant
-constexpr int GSEG = 2048;          // K elements per gram workgroup (multiple of BK)
 constexpr int KFAC_ROWBATCH = 16;   // panel layout of [M_0 | M_1 | ...] (internal to this file)
 
 struct CovJobDev {
@@ -51,25 +48,6 @@ struct CovArgs {
   CovJobDev job[CMAXJ];
 };
 static_assert(sizeof(CovArgs) <= 4096, "kernel argument block");
-
-__device__ __forceinline__ int cov_find_job(const int* ends, int njobs, int task) {
-  int j = 0;
-  while (j + 1 < njobs && task >= ends[j]) ++j;
-  return j;
-}
-
-__device__ __forceinline__ OpDev rowmajor_op(const float* p, int rows, int cols, int64_t ld) {
-  OpDev d{};
-  d.ptr = p; d.layout = KFAC_ROWMAJOR; d.rows = rows; d.cols = cols; d.ld = ld; d.ones = -1;
-  return d;
-}
-
-// element (k, i) = p[i * L + k]
-__device__ __forceinline__ OpDev channel_op(const float* p, int64_t rows, int cols, int64_t L) {
-  OpDev d{};
-  d.ptr = p; d.layout = KFAC_CHANNEL; d.rows = rows; d.cols = cols; d.L = L; d.sB = 0; d.ones = -1;
-  return d;
-}
 
 // element (k, j) = p[(j / L) * sB + k * L + j % L]: row j / L of J viewed (nA x nG), L = nG
 __device__ __forceinline__ OpDev rowbatch_op(const float* p, int rows, int cols, int64_t L, int64_t sB) {
@@ -160,35 +138,18 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_apply_u(CovArgs args) {
   }
 }
 
-// Launch 2: one 64x64 tile of T = U K2, U the (rows*nA x nG) stack
-// (A-operand element (g, i) = U[i*nG + g]).
+// Launch 2: one 64x64 tile of T = U K2, U the (rows*nA x nG) stack.
 __global__ __launch_bounds__(NTHREADS) void kfac_cov_apply_t(CovArgs args) {
   __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
   const int task = blockIdx.x;
   const CovJobDev& C = args.job[cov_find_job(args.t_end, args.njobs, task)];
   const int local = task - C.t_begin;
-  const int i0 = (local / C.tg) * TILE, g0 = (local % C.tg) * TILE;
-  const OpDev ut = channel_op(C.U, C.nG, C.trows, C.nG);
-  const OpDev k2 = rowmajor_op(C.K2, C.nG, C.nG, C.ld2);
-  floatx16 acc;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-  // T[i][g'] = sum_g U[i][g] K2[g][g']; K2 lower => g >= g0
-  contract_tile<KFAC_CHANNEL, KFAC_ROWMAJOR>(ut, i0, k2, g0, C.lower2 ? g0 : 0, C.nG, false, true,
-                                             lds, acc);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = g0 + (wave & 1) * 32 + (lane & 31);
-  if (g >= C.nG) return;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const int i = i0 + (wave >> 1) * 32 + acc_row(v, lane);
-    if (i < C.trows) C.T[(int64_t)i * C.nG + g] = acc[v];
-  }
+  cov_times_k2_tile(C.U, C.nG, C.trows, C.nG, C.K2, C.ld2, C.lower2, (local / C.tg) * TILE,
+                    (local % C.tg) * TILE, C.T, lds);
 }
 
 // Gram partial: rows c of sample b over one K segment, lower triangle of the nc x nc
-// block.  Every wave contracts its quarter of each staged panel (contract_tile's
-// narrow mode); the four partials are summed in a fixed order.
+// block.
 __global__ __launch_bounds__(NTHREADS) void kfac_cov_gram(CovArgs args) {
   __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
   const int task = blockIdx.x;
@@ -198,26 +159,8 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_gram(CovArgs args) {
   const int seg = (int)(local % C.nseg);
   const int nc = args.nc;
   const int64_t K = (int64_t)C.nA * C.nG;
-  const int64_t k0 = (int64_t)seg * GSEG, k1 = min(K, k0 + GSEG);
-  const OpDev t = channel_op(C.T + b * nc * K, K, nc, K);
-  floatx16 acc;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-  contract_tile<KFAC_CHANNEL, KFAC_CHANNEL>(t, 0, t, 0, k0, k1, true, true, lds, acc, true);
-  // (contract_tile leaves through a barrier: lds is free)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr int RP = 33;
-  static_assert(4 * 32 * RP <= 4 * PANEL, "wave partials fit the staging buffer");
-#pragma unroll
-  for (int v = 0; v < 16; ++v) lds[(wave * 32 + acc_row(v, lane)) * RP + (lane & 31)] = acc[v];
-  __syncthreads();
-  float* part = C.partial + local * nc * nc;
-  for (int e = threadIdx.x; e < nc * nc; e += NTHREADS) {
-    const int c = e / nc, c2 = e - c * nc;
-    if (c2 > c) continue;
-    const int o = c * RP + c2;
-    part[e] = (lds[o] + lds[32 * RP + o]) + (lds[64 * RP + o] + lds[96 * RP + o]);
-  }
+  const int64_t k0 = (int64_t)seg * GSEG;
+  cov_gram_segment(C.T + b * nc * K, K, nc, k0, min(K, k0 + GSEG), C.partial + local * nc * nc, lds);
 }
 
 // cov[b] (+)= sum over jobs (in job order) of the segment partials (in segment order),

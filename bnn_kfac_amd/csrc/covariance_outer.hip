@@ -1,0 +1,275 @@
+// Factored GLM predictive: a Linear layer's output covariance without its Jacobian rows.
+//
+// A Linear layer's Jacobian row is rank one: with abar_b = [a_b | 1] the layer's input
+// and delta_{b,c} = d f_c(x_b) / d z at the layer's output z, M_{b,c} = abar_b delta_{b,c}^T,
+// so T_{b,c} = K1^T M_{b,c} K2 = (K1^T abar_b)(K2^T delta_{b,c})^T and
+//   cov[b][c][c'] = sum_jobs s_j[b] * (V_{j,b} V_{j,b}^T)[c][c'] ,
+//   s_j[b] = || K1_j^T abar_{j,b} ||^2 ,   V_{j,b} = Delta_{j,b} K2_j   (nc x nG).
+// Per call (<= 8 jobs, nb samples, nc <= 32):
+//   rownorm: 64x64 tiles of Abar K1 (nb x nA by nA x nA) on contract_tile's fp32 MFMA
+//            (exact fp32 products); the product is NOT written: the epilogue squares the
+//            tile and sums it over its 64 columns into partial [job][column tile][b].
+//            The ones column of abar is synthesised by the panel loader (OpDev::ones).
+//            A lower-triangular K1 leaves column tile i0 the K-range [i0, nA).
+//   v      : V = Delta K2, kfac_cov_apply_t's tile (covariance_common.h) over the
+//            (nb*nc x nG) matrix of the delta rows
+//   gram   : V_b V_b^T, kfac_cov_gram's segment with K = nG
+//   reduce : per sample, each job's gram partials summed over segments and multiplied by
+//            s_j[b] (its column-tile partials summed in tile order in fp64), then summed
+//            over jobs in job order, all in fp64; the lower triangle is mirrored.
+// No atomics: two calls give identical bits, a sample's block depends on that sample
+// only, and every block is bitwise symmetric.
+// Rownorm tasks are ordered column-tile major, heaviest first, and run in plain block
+// order (covariance.hip's finding: per-XCD ranges put the long tiles on one XCD).
+#include "covariance_common.h"
+
+namespace kfac {
+
+constexpr int KFAC_SAMPLEROWS = 17;  // panel layout of Abar^T (internal to this file)
+
+struct OuterJobDev {
+  const float* a;
+  const float* D;
+  const float* K1;
+  const float* K2;
+  float* norm;     // at x nb: sum over column tile t of (abar_b K1)^2
+  float* V;        // nb*nc x nG
+  float* partial;  // nb x nseg x nc*nc
+  int64_t lda, ldD, ld1, ld2;
+  int cols, ones, nA, nG;  // ones = cols if has_ones else -1
+  int at, bt, tg, nseg, lower1, lower2;
+  int vrows;                       // nb*nc
+  int n_begin, v_begin, g_begin;   // first task in the rownorm / V / gram launch
+};
+
+struct OuterArgs {
+  int njobs, nc, accumulate;
+  int64_t nb;
+  float* cov;
+  int n_end[CMAXJ], v_end[CMAXJ], g_end[CMAXJ];
+  OuterJobDev job[CMAXJ];
+};
+static_assert(sizeof(OuterArgs) <= 4096, "kernel argument block");
+
+// element (k, b) = k < rows ? p[b * ld + k] : (k == ones ? 1 : 0): Abar^T, samples as
+// the operand's columns.  rows = the stored columns of a, cols = nb.
+__device__ __forceinline__ OpDev samplerows_op(const float* p, int kcols, int ones, int nb,
+                                               int64_t ld) {
+  OpDev d{};
+  d.ptr = p; d.layout = KFAC_SAMPLEROWS; d.rows = kcols; d.cols = nb; d.ld = ld; d.ones = ones;
+  return d;
+}
+
+// Panel<CHANNEL>'s thread map (32 lanes walk k, contiguous in a sample's row) with the
+// ones entry on the K axis: row k == ones of the panel is 1 for every sample.
+template <>
+struct Panel<KFAC_SAMPLEROWS> {
+  static constexpr int PITCH = LDP;
+  const float* base;
+  int64_t ld, kend;
+  int r, c0, col0, nb, krows, ones;
+  __device__ __forceinline__ void init(const OpDev& op, const float* base_, int col0_, int tid,
+                                       int64_t k_end, int64_t) {
+    base = base_; ld = op.ld; kend = k_end; nb = op.cols; krows = (int)op.rows; ones = op.ones;
+    r = tid & 31; c0 = tid >> 5; col0 = col0_;
+  }
+  __device__ __forceinline__ void load(int64_t k, float (&v)[8]) const {
+    const int64_t kk = k + r;
+    const bool ok = kk < kend;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const int b = col0 + c0 + 8 * m;
+      float x = 0.f;
+      if (ok && b < nb) x = kk < krows ? base[(int64_t)b * ld + kk] : (kk == ones ? 1.f : 0.f);
+      v[m] = x;
+    }
+  }
+  __device__ __forceinline__ void store(float* lds, const float (&v)[8]) const {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) lds[r * LDP + c0 + 8 * m] = v[m];
+  }
+};
+
+// One 64 (columns i of K1) x 64 (samples b) tile of (Abar K1)^T, squared and summed over
+// i: norm[tile i][b].  A wave's quadrant holds 32 i x 32 b with b along the lanes, so a
+// lane sums its 16 registers, adds the other half-wave's, and the two waves that share
+// the samples are added through LDS: one fixed order.
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_rownorm(OuterArgs args) {
+  __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
+  const int task = blockIdx.x;
+  const OuterJobDev& C = args.job[cov_find_job(args.n_end, args.njobs, task)];
+  const int local = task - C.n_begin;
+  const int ti = local / C.bt;
+  const int i0 = ti * TILE, b0 = (local % C.bt) * TILE;
+  const OpDev k1 = rowmajor_op(C.K1, C.nA, C.nA, C.ld1);
+  const OpDev at = samplerows_op(C.a, C.cols, C.ones, (int)args.nb, C.lda);
+  floatx16 acc;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+  // U[i][b] = sum_k K1[k][i] abar[b][k]; K1 lower => k >= i0
+  contract_tile<KFAC_ROWMAJOR, KFAC_SAMPLEROWS>(k1, i0, at, b0, C.lower1 ? i0 : 0, C.nA, false, true,
+                                                lds, acc);
+  // (contract_tile leaves through a barrier: lds is free; columns i >= nA are zero)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float s = 0.f;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) s += acc[v] * acc[v];
+  s += __shfl_xor(s, 32);
+  if (lane < 32) lds[wave * 32 + lane] = s;
+  __syncthreads();
+  if (threadIdx.x < TILE) {
+    const int qj = threadIdx.x >> 5, j = threadIdx.x & 31;
+    const int64_t b = b0 + qj * 32 + j;
+    // waves (qi, qj) = (0, qj) and (1, qj)
+    if (b < args.nb) C.norm[(int64_t)ti * args.nb + b] = lds[qj * 32 + j] + lds[(2 + qj) * 32 + j];
+  }
+}
+
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_v(OuterArgs args) {
+  __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
+  const int task = blockIdx.x;
+  const OuterJobDev& C = args.job[cov_find_job(args.v_end, args.njobs, task)];
+  const int local = task - C.v_begin;
+  cov_times_k2_tile(C.D, C.ldD, C.vrows, C.nG, C.K2, C.ld2, C.lower2, (local / C.tg) * TILE,
+                    (local % C.tg) * TILE, C.V, lds);
+}
+
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_gram(OuterArgs args) {
+  __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
+  const int task = blockIdx.x;
+  const OuterJobDev& C = args.job[cov_find_job(args.g_end, args.njobs, task)];
+  const int64_t local = task - C.g_begin;
+  const int64_t b = local / C.nseg;
+  const int seg = (int)(local % C.nseg);
+  const int nc = args.nc;
+  const int64_t K = C.nG;
+  const int64_t k0 = (int64_t)seg * GSEG;
+  cov_gram_segment(C.V + b * nc * K, K, nc, k0, min(K, k0 + GSEG), C.partial + local * nc * nc, lds);
+}
+
+// cov[b] (+)= sum over jobs (in job order) of s_j[b] * (segment partials in segment
+// order), fp64; s_j[b] = its column-tile partials in tile order, fp64.
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_reduce(OuterArgs args) {
+  __shared__ double scale[CMAXJ];
+  const int64_t b = blockIdx.x;
+  const int nc = args.nc, n2 = nc * nc;
+  if ((int)threadIdx.x < args.njobs) {
+    const OuterJobDev& C = args.job[threadIdx.x];
+    double s = 0.0;
+    for (int t = 0; t < C.at; ++t) s += (double)C.norm[(int64_t)t * args.nb + b];
+    scale[threadIdx.x] = s;
+  }
+  __syncthreads();
+  float* cov = args.cov + b * n2;
+  for (int e = threadIdx.x; e < n2; e += NTHREADS) {
+    const int c = e / nc, c2 = e - c * nc;
+    if (c2 > c) continue;
+    double total = 0.0;
+    for (int j = 0; j < args.njobs; ++j) {
+      const OuterJobDev& C = args.job[j];
+      const float* part = C.partial + b * C.nseg * n2 + e;
+      double s = 0.0;
+      for (int i = 0; i < C.nseg; ++i) s += (double)part[(int64_t)i * n2];
+      total += scale[j] * s;
+    }
+    const float v = args.accumulate ? (float)((double)cov[e] + total) : (float)total;
+    cov[e] = v;
+    cov[c2 * nc + c] = v;
+  }
+}
+
+static int64_t outer_nA(const kfac_cov_outer_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
+static int64_t outer_nseg(const kfac_cov_outer_job& j) { return cdiv(j.nG, GSEG); }
+static size_t outer_norm_bytes(const kfac_cov_outer_job& j, int64_t nb) {
+  return align_up((size_t)(cdiv(outer_nA(j), TILE) * nb) * sizeof(float), 256);
+}
+static size_t outer_v_bytes(const kfac_cov_outer_job& j, int64_t rows) {
+  return align_up((size_t)rows * (size_t)j.nG * sizeof(float), 256);
+}
+static size_t outer_partial_bytes(const kfac_cov_outer_job& j, int64_t nb, int nc) {
+  return align_up((size_t)(nb * outer_nseg(j)) * nc * nc * sizeof(float), 256);
+}
+static bool outer_job_ok(const kfac_cov_outer_job& q) {
+  return q.a && q.D && q.K1 && q.K2 && q.cols > 0 && q.nG > 0 && q.lda >= q.cols &&
+         q.ldD >= q.nG && q.ld1 >= outer_nA(q) && q.ld2 >= q.nG;
+}
+
+}  // namespace kfac
+
+using namespace kfac;
+
+extern "C" size_t kfac_kron_cov_outer_workspace_bytes(const kfac_cov_outer_job* jobs, int njobs,
+                                                      int64_t nb, int nc) {
+  if (!jobs || njobs <= 0 || njobs > CMAXJ || nb <= 0 || nc <= 0 || nc > CMAXC) return 0;
+  size_t total = 0;
+  for (int i = 0; i < njobs; ++i) {
+    if (jobs[i].cols <= 0 || jobs[i].nG <= 0) return 0;
+    total += outer_norm_bytes(jobs[i], nb) + outer_v_bytes(jobs[i], nb * nc) +
+             outer_partial_bytes(jobs[i], nb, nc);
+  }
+  return total;
+}
+
+extern "C" int kfac_kron_cov_outer(const kfac_cov_outer_job* jobs, int njobs, int64_t nb, int nc,
+                                   int accumulate, float* cov, void* workspace,
+                                   size_t workspace_bytes, kfac_stream_t stream) {
+  if (!jobs || njobs <= 0 || njobs > CMAXJ || nb <= 0 || nc <= 0 || nc > CMAXC || !cov)
+    return KFAC_EINVAL;
+  for (int i = 0; i < njobs; ++i)
+    if (!outer_job_ok(jobs[i])) return KFAC_EINVAL;
+  const int64_t lim = (int64_t)1 << 31;
+  // samples and delta rows are indexed with 32-bit columns: nb*nc (and with it every
+  // launch's task count) stays below 2^31
+  if (nb >= (lim - TILE) / nc) return KFAC_EINVAL;
+  const int64_t rows = nb * nc;
+  OuterArgs args{};
+  args.njobs = njobs;
+  args.nc = nc;
+  args.accumulate = accumulate;
+  args.nb = nb;
+  args.cov = cov;
+  int64_t nn = 0, nv = 0, ng = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const kfac_cov_outer_job& q = jobs[i];
+    if (outer_nA(q) >= lim - TILE) return KFAC_EINVAL;
+    OuterJobDev& d = args.job[i];
+    d.a = q.a; d.D = q.D; d.K1 = q.K1; d.K2 = q.K2;
+    d.lda = q.lda; d.ldD = q.ldD; d.ld1 = q.ld1; d.ld2 = q.ld2;
+    d.cols = q.cols;
+    d.ones = q.has_ones ? q.cols : -1;
+    d.nA = (int)outer_nA(q);
+    d.nG = q.nG;
+    d.at = (int)cdiv(d.nA, TILE);
+    d.bt = (int)cdiv(nb, TILE);
+    d.tg = (int)cdiv(q.nG, TILE);
+    d.nseg = (int)outer_nseg(q);
+    d.lower1 = q.lower1 != 0;
+    d.lower2 = q.lower2 != 0;
+    d.vrows = (int)rows;
+    d.n_begin = (int)nn; d.v_begin = (int)nv; d.g_begin = (int)ng;
+    nn += (int64_t)d.at * d.bt;
+    nv += cdiv(rows, TILE) * d.tg;
+    ng += nb * d.nseg;
+    if (nn >= lim || nv >= lim || ng >= lim) return KFAC_EINVAL;
+    args.n_end[i] = (int)nn; args.v_end[i] = (int)nv; args.g_end[i] = (int)ng;
+  }
+  if (!workspace || workspace_bytes < kfac_kron_cov_outer_workspace_bytes(jobs, njobs, nb, nc))
+    return KFAC_EWORKSPACE;
+  char* ws = (char*)workspace;
+  for (int i = 0; i < njobs; ++i) {
+    OuterJobDev& d = args.job[i];
+    d.norm = reinterpret_cast<float*>(ws); ws += outer_norm_bytes(jobs[i], nb);
+    d.V = reinterpret_cast<float*>(ws); ws += outer_v_bytes(jobs[i], rows);
+    d.partial = reinterpret_cast<float*>(ws); ws += outer_partial_bytes(jobs[i], nb, nc);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kfac_cov_rownorm, dim3((unsigned)nn), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_outer_v, dim3((unsigned)nv), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_outer_gram, dim3((unsigned)ng), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_outer_reduce, dim3((unsigned)nb), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}

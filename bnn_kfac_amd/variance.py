@@ -318,12 +318,175 @@ def output_jacobians(model: torch.nn.Module, layers: Sequence[torch.nn.Module], 
     return logits.detach(), Js
 
 
-def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64):
+def layer_io_jacobians(model: torch.nn.Module, layers: Sequence[torch.nn.Module], x: Tensor):
+    """(logits (n, nc), [(a_l, D_l)]): every layer's input a_l (n, ...) and the Jacobian of
+    the model's outputs at the layer's output z_l, D_l (n, nc, *z_l.shape[1:]) contiguous
+    with D_l[b, c] = d f_c(x_b) / d z_l[b], from ONE forward and one batched backward of
+    the nc one-hot output vectors to all captured outputs.  For a Linear layer the
+    Jacobian row w.r.t. [W | b] is outer([a_b | 1], D[b, c]): no row is materialised.
+
+    Assumes independent samples (no train-mode BatchNorm: d f(x_b) / d z[b'] = 0 for
+    b' != b) and that each layer is called once per forward.  Module hooks are suspended
+    and restored.  Pure torch: works on CPU tensors."""
+    layers = list(layers)
+    captured = {}
+
+    def capture(module, inputs, output):
+        if module in captured:
+            raise RuntimeError(f"{module.__class__.__name__} was called twice in one forward")
+        captured[module] = (inputs[0].detach(), output)
+        # the module's successor may work in place (nn.ReLU(inplace=True)): hand it a copy,
+        # so the captured tensor stays the layer's own output z
+        return output.clone()
+
+    with hooks_suspended(model), torch.enable_grad():
+        handles = [layer.register_forward_hook(capture) for layer in layers]
+        try:
+            xin = x.detach()
+            if xin.is_floating_point():
+                xin = xin.requires_grad_(True)  # (a frozen first layer still gets a graph)
+            y = model(xin)
+        finally:
+            for h in handles:
+                h.remove()
+        missing = [l.__class__.__name__ for l in layers if l not in captured]
+        if missing:
+            raise RuntimeError(f"layers not reached by the forward pass: {missing}")
+        n = y.shape[0]
+        y = y.reshape(n, -1)
+        nc = y.shape[1]
+        zs = [captured[layer][1] for layer in layers]
+        # grad_outputs[c] selects output c of every sample: samples are independent, so
+        # d sum_b f_c(x_b) / d z[b] = d f_c(x_b) / d z[b]
+        go = torch.zeros(nc, n, nc, dtype=y.dtype, device=y.device)
+        go[torch.arange(nc), :, torch.arange(nc)] = 1
+        grads = torch.autograd.grad(y, zs, grad_outputs=go, is_grads_batched=True, allow_unused=True)
+    out = []
+    for layer, z, g in zip(layers, zs, grads):
+        if g is None:
+            g = z.new_zeros((nc,) + tuple(z.shape))
+        out.append((captured[layer][0], g.movedim(0, 1).contiguous()))
+    return y.detach(), out
+
+
+def conv_jacobian_rows(layer: torch.nn.Conv2d, a: Tensor, D: Tensor) -> Tensor:
+    """A Conv2d layer's Jacobian rows (n, nc, nA*nG) in the posterior's order from its
+    input a (n, C, H, W) and D (n, nc, Cout, Ho, Wo) of layer_io_jacobians:
+    M_{b,c} = unfold(a_b) D_{b,c}^T, bias row sum_p D_{b,c}[:, p]."""
+    unf = torch.nn.functional.unfold(a, layer.kernel_size, dilation=layer.dilation,
+                                     padding=layer.padding, stride=layer.stride)  # (n, C*kh*kw, P)
+    n, nc, nG = D.shape[:3]
+    Dp = D.reshape(n, nc, nG, -1)
+    M = torch.einsum("bkp,bcgp->bckg", unf, Dp)
+    if layer.bias is not None:
+        M = torch.cat([M, Dp.sum(-1).unsqueeze(2)], dim=2)
+    return M.reshape(n, nc, -1)
+
+
+def kron_covariance_outer(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]], lower: bool = True,
+                          max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance for Linear layers without their Jacobian rows:
+    cov[b] = sum_l ||K1_l^T abar_l[b]||^2 (D_l[b] K2_l)(D_l[b] K2_l)^T, abar = [a | 1].
+
+    terms: [(a_l, D_l, K1_l, K2_l)] as layer_io_jacobians returns them: a (nb, cols) the
+    layer's input, D (nb, nc, nG) or (nc, nG), K1 (nA x nA) with nA = cols + 1 (bias: the
+    ones column is implicit) or nA = cols, K2 (nG x nG); `lower` marks K1 / K2
+    lower-triangular.  Returns (nb, nc, nc) fp32, every block bitwise symmetric.  More
+    than 8 terms fold in groups of 8; the samples are cut into chunks that need at most
+    `max_workspace_bytes` of scratch each (a sample's block depends on that sample only,
+    so chunking does not change a bit).
+    """
+    if not terms:
+        raise ValueError("no terms")
+    keep, jobs = [], []
+    nb = nc = None
+    for a, D, K1, K2 in terms:
+        if K1.dim() != 2 or K2.dim() != 2 or K1.shape[0] != K1.shape[1] or K2.shape[0] != K2.shape[1]:
+            raise ValueError(f"K1 {tuple(K1.shape)} / K2 {tuple(K2.shape)}: expected square matrices")
+        nA, nG = K1.shape[0], K2.shape[0]
+        D3, ldD = _cov_rows(D, nG)
+        a2 = a.detach()
+        a2 = a2.reshape(1, -1) if a2.dim() == 1 else a2
+        if a2.dim() != 2:
+            raise ValueError(f"a {tuple(a2.shape)}: expected (nb, cols), a Linear layer's 2-D input")
+        cols = a2.shape[1]
+        if nA not in (cols, cols + 1) or cols == 0:
+            raise ValueError(f"a has {cols} columns, K1 {tuple(K1.shape)} needs {nA} or {nA - 1}")
+        if nb is None:
+            nb, nc = D3.shape[0], D3.shape[1]
+        elif (D3.shape[0], D3.shape[1]) != (nb, nc):
+            raise ValueError("all terms need the same (nb, nc)")
+        if a2.shape[0] != nb:
+            raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
+        if nc > MAX_COV_CLASSES:
+            raise ValueError(f"kron_covariance_outer handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols):
+            a2 = a2.contiguous()
+        lda = a2.stride(0) if nb > 1 else cols
+        for t, what in ((a2, "a"), (D3, "D"), (K1, "K1"), (K2, "K2")):
+            N.require_device(t, what)
+        K1c = K1.detach() if K1.stride(-1) == 1 else K1.detach().contiguous()
+        K2c = K2.detach() if K2.stride(-1) == 1 else K2.detach().contiguous()
+        keep.extend([a2, D3, K1c, K2c])
+        jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0,
+                     K1c.data_ptr(), K1c.stride(0), K2c.data_ptr(), K2c.stride(0), int(lower), int(lower)))
+    out = torch.empty(nb, nc, nc, dtype=torch.float32, device=keep[0].device)
+    if nb == 0:
+        return out
+    groups = [jobs[i:i + 8] for i in range(0, len(jobs), 8)]
+
+    def need(n):
+        return max(N.kron_cov_outer_workspace_bytes([N.CovOuterJob(*j) for j in g], n, nc) for g in groups)
+
+    step = nb
+    while step > 1 and need(step) > max_workspace_bytes:
+        step = max(1, min(step - 1, step * max_workspace_bytes // need(step)))
+    if need(step) > max_workspace_bytes:
+        raise ValueError(f"one sample needs {need(1)} workspace bytes, max_workspace_bytes is "
+                         f"{max_workspace_bytes}")
+    for b0 in range(0, nb, step):
+        n = min(step, nb - b0)
+        for gi, g in enumerate(groups):
+            arr = [N.CovOuterJob(j[0] + 4 * b0 * j[1], j[1], j[2], j[3], j[4] + 4 * b0 * nc * j[5], *j[5:])
+                   for j in g]
+            N.kron_cov_outer(arr, n, nc, out[b0:b0 + n], accumulate=gi > 0)
+    return out
+
+
+def _glm_chunk_factored(model, layers, inv, x):
+    """One chunk of the factored route: Linear layers by kron_covariance_outer, Conv2d
+    layers by kron_covariance on rows built from the same captures; the two are added."""
+    f, io = layer_io_jacobians(model, layers, x)
+    outer, dense = [], []
+    for layer, (a, D) in zip(layers, io):
+        if isinstance(layer, torch.nn.Linear):
+            if a.dim() != 2:
+                raise ValueError(f"the factored route needs 2-D Linear inputs, got {tuple(a.shape)}")
+            outer.append((a, D, *inv[layer]))
+        elif isinstance(layer, torch.nn.Conv2d):
+            dense.append((conv_jacobian_rows(layer, a, D), *inv[layer]))
+        else:
+            raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
+                             f"{layer.__class__.__name__}")
+    cov = kron_covariance_outer(outer, lower=True) if outer else None
+    if dense:
+        conv = kron_covariance(dense, lower=True)
+        cov = conv if cov is None else cov + conv
+    return f, cov
+
+
+def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64, jacobians: str = "dense"):
     """The linearised (GLM) predictive of `kfac.model` under the KFAC posterior
     (KFAC.invert's factors, the Gaussian KFAC.sample draws from): (logits (N, nc),
     cov (N, nc, nc)) with cov = sum_l J_l (L_A L_A^T kron L_G L_G^T) J_l^T, in chunks
     of `chunk` samples.  No sampling loop, no weight replacement; a regression net
-    with one output has its predictive variance in cov[:, 0, 0]."""
+    with one output has its predictive variance in cov[:, 0, 0].
+
+    jacobians="dense" materialises every Jacobian row (output_jacobians); "factored"
+    takes one layer_io_jacobians call per chunk and never forms a Linear layer's rows
+    (kron_covariance_outer), which is what a wide layer needs."""
+    if jacobians not in ("dense", "factored"):
+        raise ValueError(f"jacobians must be 'dense' or 'factored', got {jacobians!r}")
     model = kfac.model
     if layers is None:
         layers = [m for m in list(model.modules())[1:] if m in kfac.state]
@@ -331,6 +494,11 @@ def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64):
     inv = kfac.inv_state
     logits, covs = [], []
     for c0 in range(0, x.shape[0], chunk):
+        if jacobians == "factored":
+            f, cov = _glm_chunk_factored(model, layers, inv, x[c0:c0 + chunk])
+            logits.append(f)
+            covs.append(cov)
+            continue
         f, Js = output_jacobians(model, layers, x[c0:c0 + chunk])
         logits.append(f)
         covs.append(kron_covariance([(J, *inv[layer]) for layer, J in zip(layers, Js)], lower=True))

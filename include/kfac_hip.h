@@ -248,6 +248,40 @@ KFAC_API size_t kfac_kron_cov_workspace_bytes(const kfac_cov_job* jobs, int njob
 KFAC_API int kfac_kron_cov(const kfac_cov_job* jobs, int njobs, int64_t nb, int nc, int accumulate,
                   float* cov, void* workspace, size_t workspace_bytes, kfac_stream_t stream);
 
+/* ------------------------------- GLM predictive covariance, factored (Linear layers)
+ * The same covariance for layers whose Jacobian row is rank one, without the rows.  For
+ * a Linear layer M_{b,c} = abar_b delta_{b,c}^T, abar_b = [a_b | 1] the layer's input and
+ * delta_{b,c} = d f_c(x_b) / d z at the layer's output z, so K1^T M K2 =
+ * (K1^T abar_b)(K2^T delta_{b,c})^T and
+ *   cov[b] (+)= sum_j s_j[b] * V_{j,b} V_{j,b}^T ,
+ *   s_j[b] = || K1_j^T abar_{j,b} ||^2 ,   V_{j,b} = Delta_{j,b} K2_j   (nc x nG),
+ * Delta_{j,b} the nc rows delta_{b,c}.  Only row-major (Linear) inputs are covered: a
+ * Conv2d layer's row is a sum over positions and goes through kfac_kron_cov.
+ * s_j[b] is summed over 64-column tiles of abar K1 in tile order, V V^T over K segments
+ * in segment order, the jobs in job order, all in fp64 and without atomics: two calls
+ * give identical bits, a sample's block depends on that sample only, and every nc x nc
+ * block is bitwise symmetric (the lower triangle is computed and mirrored).
+ * accumulate: cov += the sum, else cov = it.  At most 8 jobs and nc <= 32 per call. */
+typedef struct kfac_cov_outer_job {
+  const float* a; /* nb x cols row-major, row stride lda: the layer's input */
+  int64_t lda;
+  int32_t cols, has_ones; /* nA = cols + has_ones (implicit ones column last) */
+  const float* D; /* row r = b*nc + c at D + r*ldD: nG elements, d f_c(x_b) / d z[g] */
+  int64_t ldD;
+  int32_t nG, reserved;
+  const float* K1; /* nA x nA */
+  int64_t ld1;
+  const float* K2; /* nG x nG */
+  int64_t ld2;
+  int32_t lower1, lower2; /* K1 / K2 lower-triangular: their zero K-range is skipped */
+} kfac_cov_outer_job;
+
+KFAC_API size_t kfac_kron_cov_outer_workspace_bytes(const kfac_cov_outer_job* jobs, int njobs,
+                                                    int64_t nb, int nc);
+KFAC_API int kfac_kron_cov_outer(const kfac_cov_outer_job* jobs, int njobs, int64_t nb, int nc,
+                                 int accumulate, float* cov, void* workspace, size_t workspace_bytes,
+                                 kfac_stream_t stream);
+
 /* -------------------------------------------------------- posterior samples
  * out_j = (LA_j Z_j LG_j^T)^T, shape (nG x nA): KFAC.sample, curvatures.py:400-405,
  * with Z (nA x nG row-major) supplied by the caller (torch.randn, the reference's

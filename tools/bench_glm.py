@@ -4,6 +4,8 @@ Workloads (random init, KFAC factors accumulated over synthetic batches, inverte
 (0.04, 200)):
   mlp       : the MNIST MLP 784-128-10 (layers 785x128, 129x10), nb = 64, nc = 10
   basenet15k: BaseNet_15k's four layers (26x5, 126x10, 161x80, 81x10), nb = 256, nc = 10
+  c5        : the wide MLP 784-4096-4096-10 (layers 785x4096, 4097x4096, 4097x10), nb = 64,
+              nc = 10, factored route only (one dense Jacobian row of it is 67 MB)
 
 Per workload, on the same Jacobians and factors:
   cov_ms        : kron_covariance (kfac_kron_cov) alone
@@ -12,6 +14,12 @@ Per workload, on the same Jacobians and factors:
   cpu_cov_ms    : that composition in fp32 on the host, 16 threads
   glm_ms        : glm_predictive end to end (vmapped Jacobians + kron_covariance)
   torch_glm_ms  : the same Jacobians + the torch composition
+The factored route (glm_predictive(jacobians="factored")), the two routes alternated call
+by call in one session:
+  cov_linear_dense_ms / cov_linear_outer_ms : the Linear layers alone, kron_covariance on
+                  their dense rows against kron_covariance_outer on (input, output Jacobian)
+  glm_dense_ms / glm_factored_ms : glm_predictive end to end, both ways
+  factored_max_diff_over_max : the two end-to-end covariances, max |diff| / max
 GPU times are HIP-event times of single calls after a warm-up, medians over `--reps`
 calls.  apply_flops / gram_bytes are the algorithmic work (2 nA^2 nG + 2 nA nG^2 per
 row, halved for the skipped triangle; T read once) for a roofline over kernel times
@@ -30,7 +38,8 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bnn_kfac_amd import _native as N  # noqa: E402
 from bnn_kfac_amd.curvatures import KFAC  # noqa: E402
-from bnn_kfac_amd.variance import glm_predictive, kron_covariance, output_jacobians  # noqa: E402
+from bnn_kfac_amd.variance import (glm_predictive, kron_covariance, kron_covariance_outer,  # noqa: E402
+                                   layer_io_jacobians, output_jacobians)
 
 
 def mlp():
@@ -41,6 +50,29 @@ def basenet15k():
     return nn.Sequential(nn.Conv2d(1, 5, 5), nn.ReLU(), nn.MaxPool2d(2), nn.Conv2d(5, 10, 5), nn.ReLU(),
                          nn.MaxPool2d(2), nn.Flatten(), nn.Linear(160, 80), nn.ReLU(),
                          nn.Linear(80, 10)), (1, 28, 28), 256
+
+
+def c5():
+    return nn.Sequential(nn.Linear(784, 4096), nn.ReLU(), nn.Linear(4096, 4096), nn.ReLU(),
+                         nn.Linear(4096, 10)), (784,), 64
+
+
+def alternate_ms(fns, warmup, reps):
+    """Medians of HIP-event times of each of `fns`, called in turn `reps` times."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(reps):
+        for fn, t in zip(fns, times):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            t.append(a.elapsed_time(b))
+    return [statistics.median(t) for t in times]
 
 
 def event_ms(fn, warmup, reps):
@@ -67,7 +99,7 @@ def torch_cov(terms):
     return cov
 
 
-def run(name, make, dev, args):
+def fit(make, dev):
     torch.manual_seed(0)
     net, xshape, nb = make()
     net = net.to(dev)
@@ -81,7 +113,26 @@ def run(name, make, dev, args):
         kfac.update(256)
     kfac.invert(0.04, 200)
     layers = [m for m in list(net.modules())[1:] if m in kfac.state]
-    x = torch.rand(nb, *xshape, device=dev)
+    return net, kfac, layers, torch.rand(nb, *xshape, device=dev), nb
+
+
+def outer_terms(net, kfac, layers, x):
+    _, io = layer_io_jacobians(net, layers, x)
+    return [(a, D, *kfac.inv_state[l]) for l, (a, D) in zip(layers, io) if isinstance(l, nn.Linear)]
+
+
+def run_factored_only(make, dev, args):
+    net, kfac, layers, x, nb = fit(make, dev)
+    terms = outer_terms(net, kfac, layers, x)
+    res = {"nb": nb, "nc": terms[0][1].shape[1], "layers": [[t[2].shape[0], t[3].shape[0]] for t in terms]}
+    res["cov_linear_outer_ms"] = event_ms(lambda: kron_covariance_outer(terms), args.warmup, args.reps)
+    res["glm_factored_ms"] = event_ms(lambda: glm_predictive(kfac, x, chunk=nb, jacobians="factored"),
+                                      args.warmup, args.reps)
+    return res
+
+
+def run(name, make, dev, args):
+    net, kfac, layers, x, nb = fit(make, dev)
     _, Js = output_jacobians(net, layers, x)
     terms = [(J.contiguous(), *kfac.inv_state[l]) for l, J in zip(layers, Js)]
     nc = Js[0].shape[1]
@@ -94,6 +145,16 @@ def run(name, make, dev, args):
     res["torch_cov_ms"] = event_ms(lambda: torch_cov(terms), args.warmup, args.reps)
     got, want = kron_covariance(terms), torch_cov(terms)
     res["max_diff_vs_torch_over_max"] = float((got - want).abs().max() / want.abs().max())
+    lin = [t for l, t in zip(layers, terms) if isinstance(l, nn.Linear)]
+    outer = outer_terms(net, kfac, layers, x)
+    res["cov_linear_dense_ms"], res["cov_linear_outer_ms"] = alternate_ms(
+        [lambda: kron_covariance(lin), lambda: kron_covariance_outer(outer)], args.warmup, args.reps)
+    res["glm_dense_ms"], res["glm_factored_ms"] = alternate_ms(
+        [lambda: glm_predictive(kfac, x, chunk=nb),
+         lambda: glm_predictive(kfac, x, chunk=nb, jacobians="factored")], args.warmup, args.reps)
+    dense_cov = glm_predictive(kfac, x, chunk=nb)[1]
+    fact_cov = glm_predictive(kfac, x, chunk=nb, jacobians="factored")[1]
+    res["factored_max_diff_over_max"] = float((dense_cov - fact_cov).abs().max() / dense_cov.abs().max())
     res["glm_ms"] = event_ms(lambda: glm_predictive(kfac, x, chunk=nb), 2, max(3, args.reps // 4))
 
     def torch_glm():
@@ -125,6 +186,8 @@ def main():
     out = {"workload": "GLM predictive covariance", "lib": N.LIB_PATH}
     for name, make in (("mlp", mlp), ("basenet15k", basenet15k)):
         out[name] = run(name, make, dev, args)
+    if args.only == "all":
+        out["c5"] = run_factored_only(c5, dev, args)
     print(json.dumps(out))
 
 
