@@ -22,8 +22,7 @@
 namespace kfac {
 
 struct Plan {
-  int tiles, splits;  // splits: slabs per tile (x3 thin jobs: splits - xsplits full K-splits)
-  int xsplits;
+  int tiles, splits;  // splits: slabs per tile
   int units;  // workgroups per K-split: tiles, or a staged conv job's block groups
   int tasks;  // workgroups of the job
   int64_t chunk;
@@ -145,9 +144,16 @@ static bool syrk3_group(const kfac_factor_job* jobs, int njobs) {
 // 1.34e7 vs 1.39e7 img/s with x3 in round 5; with round 6's conv kernels the pass is
 // 2.01-2.02 vs 2.06 ms with x3 (0.26 vs 0.31 ms of fc factors, 3 reps alternating,
 // `profiles/r06z13/`), so the threshold moved from 512 to 256.
+// A group whose largest factor has more than X3_PMAX panels (n > 2048: with
+// kfac_factor_syrk3 switched off), or whose distinct unit tables do not fit one launch's
+// arguments, keeps the fp32 kernel too.
 static bool tiles_x3_group(const kfac_factor_job* jobs, int njobs) {
   const int knob = knobs().tiles_x3;
-  return knob != 0 && x3_eligible_nmax(jobs, njobs) >= (knob == 1 ? 33 : 256);
+  const int nmax = x3_eligible_nmax(jobs, njobs);
+  if (knob == 0 || nmax < (knob == 1 ? 33 : 256) || x3_panels(nmax) > X3_PMAX) return false;
+  int n[MAXJ];
+  for (int i = 0; i < njobs; ++i) n[i] = factor_n(jobs[i]);
+  return x3_table_entries(n, njobs) <= X3_UCAP;
 }
 
 // A conv job on a kernel whose tasks own whole images: its family and geometry into `r`.
@@ -226,26 +232,19 @@ static void plan_jobs(const kfac_factor_job* jobs, int njobs, const Route& route
   for (int i = 0; i < njobs; ++i) {
     const int n = factor_n(jobs[i]);
     const int64_t t = cdiv(n, TILE);
-    units[i] = s3 ? syrk3_units(n) : x3 ? x3_units(n, (int)t) : fam.images ? route.cg.units : t * (t + 1) / 2;
+    units[i] = s3 ? syrk3_units(n) : x3 ? x3_units(n) : fam.images ? route.cg.units : t * (t + 1) / 2;
   }
-  // x3 jobs with thin-row pairs: the pair units are the slowest (30 MFMAs on 3
-  // fragments per 16 rows: 1,606 vs 1,434 ns per stage for a full tile, profiles/r04am/),
-  // so they take f/k more K-splits (x3_xsplits) and end with the full tiles
-  auto thin = [&](int i) { return x3 && x3_thin(factor_n(jobs[i]), (int)cdiv(factor_n(jobs[i]), TILE)); };
-  auto xs_of = [&](int i, int64_t S) { return thin(i) ? x3_xsplits(S) : 0; };
-  // workgroups of job i at `splits` slabs per tile
-  auto job_tasks = [&](int i, int64_t splits) {
-    const int64_t xs = xs_of(i, splits);
-    const int t = (int)cdiv(factor_n(jobs[i]), TILE);
-    return units[i] * (splits - xs) + (int64_t)(t - 1) * xs * (xs > 0);
+  // a factor whose last 64-column tile row holds one 32-column panel (the MNIST MLP's 785
+  // and 129): see max_rounds below
+  auto thin = [&](int i) {
+    const int n = factor_n(jobs[i]);
+    return x3 && n > TILE && (n - 1) % TILE < 32;
   };
+  // workgroups of job i at `splits` slabs per tile
+  auto job_tasks = [&](int i, int64_t splits) { return units[i] * splits; };
   // (kfac_factor_tiles_x3: narrow jobs (n <= 32) at 4x the chunk's K-splits measured ~1 %
   // slower on the MLP line, profiles/r04ah/)
-  auto job_splits = [&](int i, int64_t c) {
-    const int64_t st = job_stages(jobs[i]);
-    const int64_t sp = cdiv(st, c);
-    return thin(i) ? std::min(st, sp + sp / X3_PAIR_XS) : sp;
-  };
+  auto job_splits = [&](int i, int64_t c) { return cdiv(job_stages(jobs[i]), c); };
   auto tasks_at = [&](int64_t c) {
     int64_t n = 0;
     for (int i = 0; i < njobs; ++i)
@@ -253,9 +252,10 @@ static void plan_jobs(const kfac_factor_job* jobs, int njobs, const Route& route
     return n;
   };
   int64_t best_c = std::max(MIN_CHUNK, max_steps), best_cost = -1;
-  // (kfac_factor_tiles_x3 groups with thin-row pairs: one round -- MNIST MLP, same box:
-  // 163.4 vs 170.3 / 167.4 us per launch at the two rounds the cost model picks; other
-  // x3 groups keep the cost model's choice, which nothing measured against)
+  // (kfac_factor_tiles_x3 groups with such a factor: one round -- MNIST MLP, same box:
+  // 163.4 vs 170.3 / 167.4 us per launch at the two rounds the cost model picks, measured
+  // on the 64 x 64 tile units this kernel had before its panel cliques and not again
+  // since; other x3 groups keep the cost model's choice, which nothing measured against)
   bool any_thin = false;
   for (int i = 0; i < njobs; ++i) any_thin |= thin(i);
   // (kfac_factor_syrk3 groups, 2 workgroups per CU: up to 16 rounds, so a launch of
@@ -280,8 +280,7 @@ static void plan_jobs(const kfac_factor_job* jobs, int njobs, const Route& route
     const int64_t steps = job_stages(jobs[i]);
     if (jobs[i].acc) {
       p.splits = jobs[i].acc_splits;
-      p.xsplits = (int)xs_of(i, p.splits);
-      p.chunk = cdiv(steps, (int64_t)(p.splits - p.xsplits));
+      p.chunk = cdiv(steps, (int64_t)p.splits);
       p.slab_bytes = 0;  // partials go to the caller's accumulator
       p.tasks = (int)job_tasks(i, p.splits);
       continue;
@@ -306,8 +305,7 @@ static void plan_jobs(const kfac_factor_job* jobs, int njobs, const Route& route
       k = std::min(k, cg.B);
       p.splits = (int)cdiv(cg.B, k);
     }
-    p.xsplits = (int)xs_of(i, p.splits);
-    p.chunk = cdiv(steps, (int64_t)(p.splits - p.xsplits));
+    p.chunk = cdiv(steps, (int64_t)p.splits);
     p.slab_bytes = align_up((size_t)p.tiles * p.splits * TILE * TILE * sizeof(float), 256);
     p.tasks = (int)job_tasks(i, p.splits);
   }
@@ -384,9 +382,8 @@ static int prepare_group(const kfac_factor_job* jobs, int njobs, const Route& ro
     FactorJobDev& d = args.job[i];
     fill_dev(d, jb);
     d.glds = job_glds(jb);
-    d.x3pair = route.family == KFAC_PROF_FACTOR_X3 && x3_thin(d.n, d.t);
+    d.x3units = route.family == KFAC_PROF_FACTOR_X3 ? plans[i].units : 0;  // (x3tab: launch_tiles_x3)
     d.splits = plans[i].splits;
-    d.xsplits = plans[i].xsplits;
     d.sstride = jb.acc && jb.acc_stride > 0 ? jb.acc_stride : d.splits;
     d.chunk = plans[i].chunk;
     if (d.nseg > 1) {  // kfac_factor_update keeps a launch within KSEG batch bases

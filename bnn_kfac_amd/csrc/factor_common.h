@@ -14,6 +14,7 @@ namespace kfac {
 // factor jobs per launch.  The kernel arguments (measured kernarg_segment_size) are
 // 4,744 B for the FactorArgs kernels and 5,608 B for those that take a ConvGeom too:
 // 4,488 B of FactorArgs, 864 B of ConvGeom, 256 B of implicit arguments.
+// (kfac_factor_tiles_x3 takes its unit tables too: 8,192 B of X3Units.)
 constexpr int MAXJ = 16;
 constexpr int KSEG = 64;  // batch base pointers per launch (multi-batch jobs; +512 B)
 
@@ -33,10 +34,9 @@ struct FactorJobDev {
   int tile_begin;    // first global tile of this job (reduce launch)
   int accum;         // deferred reduction: `slab` is the caller's accumulator
   float sbeta;       // accumulator update: slab = sbeta*slab + alpha*partial
-  int x3pair;        // kfac_factor_tiles_x3: thin last tile row, diagonal + edge tiles paired
+  int x3tab;         // kfac_factor_tiles_x3: first entry of this job's unit table in X3Units::u
   int sstride;       // slabs per tile of `slab` (a job's split s of tile t: t * sstride + s)
-  int xsplits;       // x3 thin-row pairs: of the `splits` slabs per tile, the last xsplits are
-                     // written by extra, shorter K-splits of the pair units only (x3_xsplits)
+  int x3units;       // kfac_factor_tiles_x3: units (workgroups per K-split) of that table
   // ragged last batch (x.last_rows, kfac_factor_tiles_x3 / narrow tasks only): its first
   // stage `rstage` (-1: none); its rows weigh rows / last_rows = `rw` times the others'
   // (its own per-batch mean): a task crossing into it scales its sums by 1 / rw = `rinv`
@@ -307,21 +307,34 @@ constexpr int S3D_WGS = 2;  // (49 KB of LDS each)
 int64_t syrk3_units(int n);
 int launch_syrk3(const FactorArgs& args, int tasks, hipStream_t stream);
 
-// factor_tiles_x3.hip: kfac_factor_tiles_x3.  Its work units of a factor of n over
-// T = ceil(n / 64) tiles per edge: the lower-triangle tiles, or with a thin last tile row
-// (T >= 2 and at most 32 rows in it) the T-1 pairs (i, i) + (T-1, i), the other strictly
-// lower tiles of rows < T-1 and the corner (see X3_PAIR)
-constexpr int X3_WGS = 4;  // (of two waves -- 3 or 2 measured slower)
-static inline bool x3_thin(int n, int T) { return T >= 2 && n - TILE * (T - 1) <= 32; }
-// a thin-row x3 job with f full-tile K-splits gets S = f + f / k slabs per tile, the last
-// f / k of them written by extra K-splits of its pair units only; k = 5 (MNIST MLP, same
-// box, 200 steps: 3 / 5 / 10 / none 145.7 / 145.6 / 150.0 / 153.1 us per launch,
-// DESIGN.md 3.1c)
-constexpr int X3_PAIR_XS = 5;
-// S / (k + 1) recovers f / k from S = f + f / k (f = k a + b, b <= k - 1)
-static inline int64_t x3_xsplits(int64_t S) { return S / (X3_PAIR_XS + 1); }
-__host__ __device__ inline int x3_units_of(int T, bool pair) { return T * (T + 1) / 2 - (pair ? T - 1 : 0); }
-static inline int x3_units(int n, int T) { return x3_units_of(T, x3_thin(n, T)); }
+// factor_tiles_x3.hip: kfac_factor_tiles_x3.  Its work units of a factor of n are panel
+// cliques: the factor's P = ceil(n / 32) column panels of 32 are the vertices of a complete
+// graph whose edge (p, q) is the 32 x 32 block (p, q), and a unit is a clique of up to four
+// panels whose workgroup splits each panel's fragment once and multiplies every pair of
+// them -- a K4 is 6 blocks on 4 splits where a 64 x 64 tile is 4 blocks on 4.  The table of
+// a P is an exact partition of the lower triangle: every block p > q in exactly one K4, K3
+// or K2, every diagonal block in exactly one diagonal unit (up to four panels' (p, p)).
+// P = 25 (the MNIST MLP's 785) is the Steiner system S(2, 4, 25): 50 K4 units, 200 fragment
+// splits for its 300 off-diagonal blocks; other P are packed greedily in a fixed order.
+// One 32-bit entry per unit: panel s in bits 6s .. 6s+5 (unused slots repeat the last
+// panel), the number of panels in bits 24-26, bit 28 a diagonal unit.
+constexpr int X3_WGS = 4;     // (of two waves -- 3 or 2 measured slower)
+constexpr int X3_PMAX = 64;   // panels per edge the 6-bit panel fields hold (n <= 2048)
+constexpr int X3_UCAP = 2048; // table entries one launch carries (8 KB of kernel arguments)
+constexpr uint32_t X3_DIAG = 1u << 28;
+struct X3Units {
+  uint32_t u[X3_UCAP];
+};
+__host__ __device__ inline int x3_unit_np(uint32_t u) { return (int)(u >> 24) & 7; }
+__host__ __device__ inline int x3_unit_panel(uint32_t u, int s) { return (int)(u >> (6 * s)) & 63; }
+static inline int x3_panels(int n) { return (n + 31) / 32; }
+// the unit table of P panels (2 <= P <= X3_PMAX; built once per P, then shared) -- K4
+// units first, then the diagonal units, K3 and K2: the longest first
+int x3_unit_table(int P, const uint32_t** table);
+// units of a factor of n (n <= 32: the one narrow task)
+int x3_units(int n);
+// entries the distinct tables of a launch group's factors take (<= X3_UCAP to launch)
+int x3_table_entries(const int* n, int njobs);
 int launch_tiles_x3(const FactorArgs& args, int tasks, hipStream_t stream);
 
 // factor_conv.hip: kfac_factor_conv (fp32 MFMA, images staged in LDS; PATCH and CHANNEL).

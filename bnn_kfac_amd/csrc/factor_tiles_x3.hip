@@ -1,4 +1,7 @@
+#include <algorithm>
+#include <mutex>
 #include <type_traits>
+#include <vector>
 
 #include "bf16x3.h"
 #include "factor_common.h"
@@ -6,21 +9,21 @@
 namespace kfac {
 
 // ------------------------------- fp32 operands, bf16x3 products split in registers
-// kfac_factor_tiles_x3: TWO waves per 64 x 64 tile, each computing the WHOLE tile over
-// its own 16-row half of every 32-row stage.  A lane loads its MFMA fragment -- 8
-// consecutive k of one column -- straight from global memory into registers (no LDS),
-// splits it (split3: the exact three-part split of the bf16x3 kernels above) and the
-// wave runs six v_mfma_f32_32x32x16_bf16 per 32 x 32 block: 24 MFMAs of 32 cycles per
-// wave and 16-row half, against the fp32 kernel's 4 waves x 8 fp32 MFMAs of 64 cycles
-// for the same work, with no split pass and no padded images (the n <= 1024 factors,
-// where kfac_split3's HBM round trip costs as much as the products).  The two waves'
-// partial tiles are summed through LDS in a fixed order at the end.
+// kfac_factor_tiles_x3: TWO waves per work unit, each computing ALL the unit's blocks over
+// its own 16-row half of every 32-row stage.  A unit is a clique of up to four 32-column
+// panels of the factor (factor_common.h, x3_unit_table): a lane loads its MFMA fragment of
+// each panel -- 8 consecutive k of one column -- straight from global memory into
+// registers (no LDS), splits it (split3: the exact three-part split of the bf16x3 kernels
+// above) and the wave runs six v_mfma_f32_32x32x16_bf16 per 32 x 32 block between two of
+// the panels: a K4 unit is 36 MFMAs on 4 splits per wave and 16-row half, where the
+// 64 x 64 tile units this kernel had before were 24 on 4 (7.3 split VALU per MFMA: the
+// kernel is bound by its issue port, not by the matrix cores).  The two waves' partial
+// blocks are summed through LDS in a fixed order at the end.
 // Measured on the MNIST MLP group (profiles/r03_x3/ab/probe_summary.txt): direct loads
 // beat LDS-DMA rings (shared, one barrier per stage, or one per wave without a
 // barrier: 179 vs 196-204 us per 32,768-row launch), the compiled split beats a
 // hand-ordered asm one, and 128 x 128 macro tiles with the split made once per macro
-// tile into the syrk3 LDS image (x3m) lost (224 us).  The kernel is issue-bound: two
-// waves per SIMD keep its issue port ~90 % busy with 7.3 split VALU per MFMA.
+// tile into the syrk3 LDS image (x3m) lost (224 us).
 constexpr int X3_THREADS = 128;
 
 constexpr int X3_NW = X3_THREADS / 64;
@@ -43,25 +46,22 @@ __device__ __forceinline__ void x3_load8(float (&x)[8], __amdgpu_buffer_rsrc_t r
     x[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, c.voff, sbase + r * sstep, 0));
 }
 
-// The stage loop (round 4): software-pipelined segments in ONE straight-line block.
-// The fragments of the stage's first block -- A0 (and B0) -- are split during the
-// previous stage; every segment is the six MFMAs of one block interleaved
-// (sched_group_barrier) with the split of a fragment a later block needs, and that
-// fragment's registers are reloaded as soon as its split has read them:
-//   full tile (mask 15):  (0,0) | split A1    (1,0) | split B1    (0,1) | split A0'
-//                         (1,1) | split B0'
-// so each load goes out one whole stage before its split (x1, x3 hold the next stage,
-// x0, x2 the one after), at most five fragments are live and no register set is copied
-// (2 waves per SIMD at <= 200 VGPRs leave an inversion wave room beside them).  Round 3's
-// loop split all four fragments at the top of the stage, copied a 32-register prefetch
-// set into the working set every stage, branched per stage (last stage, batch change,
-// fill columns with 64-bit compares), and the compiler sank every load to the end of
-// the body and waited vmcnt(0) at the loop head: ~100 extra VALU and the whole L2
-// latency per stage.  Now every load is unconditional: past the task's range the
-// cursor stops (the last stage reloads itself), a batch change is a scalar select (the
-// next batch's base fetched a stage ahead), columns past the operand load from past
-// the buffer's record limit (0), and the ones column (FILL: only the tasks whose
-// fragments hold it) is a select of 1 / 0 by row validity.
+// The stage loop: software-pipelined segments in ONE straight-line block.  The fragments
+// of the stage's first block -- F0 and F1 -- are split during the previous stage; every
+// segment is the six MFMAs of one block interleaved (sched_group_barrier) with the split
+// of a fragment a later block needs, and that fragment's registers are reloaded as soon
+// as its split has read them:
+//   K4:  (1,0) | split F2    (2,0) | split F3    (3,0)
+//        (2,1) | split F0'   (3,1)               (3,2) | split F1'
+// (F0 and F1 each end before the next stage's is split: four split fragments live)
+// so each load goes out one whole stage before its split (x2, x3 hold the next stage,
+// x0, x1 the one after) and no register set is copied (2 waves per SIMD at <= 200 VGPRs
+// leave an inversion wave room beside them).
+// Every load is unconditional: past the task's range the cursor stops (the last stage
+// reloads itself), a batch change is a scalar select (the next batch's base fetched a
+// stage ahead), columns past the operand load from past the buffer's record limit (0),
+// and the ones column (FILL: only the units whose panels hold it) is a select of 1 / 0 by
+// row validity.
 // Microbench: tools/microbench/x3w_mb.hip; DESIGN.md §3.1c.
 struct X3Cursor {  // a stage to load: batch `seg` (base `b`), first row `k`
   const float* b;
@@ -79,28 +79,21 @@ __device__ __forceinline__ void x3_pattern() {  // 6 MFMAs, NV VALU each, the re
   }
 }
 
-// X3_PAIR: a factor whose last tile row is thin (n - 64 (T-1) <= 32: one block row,
-// the MNIST MLP's 785 and 129) pairs diagonal tile (i, i) with edge tile (T-1, i) in ONE
-// task: fragments A0, A1 (panel i) and C0 (panel T-1, block 0), five blocks
-//   D00 = A0 A0, D10 = A1 A0, D11 = A1 A1 (tile (i, i)), E00 = C0 A0, E01 = C0 A1
-// -- 30 MFMAs on 3 fragments per 16 rows, where the diagonal task alone did 18 on 2
-// and the edge task 12 on 3 (both ran ahead of the full tiles, widening each XCD's
-// L2 working set), and T-1 fewer tasks per K-split.  acc[0][0] D00, acc[1][0] D10,
-// acc[1][1] D11, acc[0][1] E00, acc4 E01; called with ti = i, tj = T-1.
-constexpr int X3_PAIR = 16;
+// The unit kinds the loop is compiled for: a clique of NP = 4, 3 or 2 panels (every block
+// (i, j), i > j, between its panel slots; the slots ascend, so slot i is the block's row
+// panel), or the diagonal blocks (s, s) of four panel slots.  Accumulators, in order:
+//   K4: (1,0) (2,0) (2,1) (3,0) (3,1) (3,2);  K3 and K2: the first 3 / 1 of them;
+//   X3_KDIAG: (0,0) (1,1) (2,2) (3,3).
+constexpr int X3_KDIAG = 0;
+constexpr int X3_NACC = 6;  // (a K4's: the LDS hand-off's slots)
+__host__ __device__ constexpr int x3_kind_blocks(int kind) { return kind == X3_KDIAG ? 4 : kind * (kind - 1) / 2; }
 
-template <int MASK, bool FILL>
-__device__ __forceinline__ void x3_loop(const FactorJobDev& J, const float* const* segs, int ti, int tj,
-                                        int64_t s0, int64_t s1, floatx16 (&acc)[2][2], floatx16& acc4) {
-  constexpr bool PAIR = MASK == X3_PAIR;
-  constexpr bool A00 = MASK & 1, A01 = MASK & 2, A10 = MASK & 4, A11 = MASK & 8;
-  constexpr bool ROW1 = A10 || A11 || PAIR, COL1 = A01 || A11;
-  // masks 13 and 1 occur on diagonal tiles only (an off-diagonal tile with block
-  // (1, 1), or with any block, has (0, 1)): B fragments = A fragments
-  constexpr bool SAME = MASK == 13 || MASK == 1;
-  static_assert(A00 || PAIR, "block (0, 0) always has work");
-  // fragments: 0 A block 0, 1 A block 1, 2 B block 0, 3 B block 1 (PAIR: 2 = C0)
-  constexpr bool USE[4] = {true, ROW1, !SAME, !SAME && COL1};
+template <int KIND, bool FILL>
+__device__ __forceinline__ void x3_loop(const FactorJobDev& J, const float* const* segs, const int (&pn)[4],
+                                        int64_t s0, int64_t s1, floatx16 (&acc)[x3_kind_blocks(KIND)]) {
+  constexpr bool DIAG = KIND == X3_KDIAG;
+  constexpr int NP = DIAG ? 4 : KIND;
+  static_assert(NP >= 2 && NP <= 4, "a unit has two to four panel slots");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ld4 = (int)J.x.ld * 4;
@@ -113,14 +106,14 @@ __device__ __forceinline__ void x3_loop(const FactorJobDev& J, const float* cons
   bool onesl[4];
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
-    const int c = (f < 2 ? ti : tj) * TILE + (f & 1) * 32 + (lane & 31);
+    const int c = pn[f] * 32 + (lane & 31);
     voff[f] = c < J.x.cols ? lr * ld4 + c * 4 : rec;  // past the operand: the zero tail
     onesl[f] = c == J.x.ones;
   }
   const int ns = (int)(s1 - s0);
   const int lastseg = J.nseg - 1;
-  // stage cursors: c1 = the next stage to load for fragments 1 / 3, c2 = the one after
-  // (fragments 0 / 2); nb = the base of the batch after c2's
+  // stage cursors: c1 = the next stage to load for fragments 2 / 3, c2 = the one after
+  // (fragments 0 / 1); nb = the base of the batch after c2's
   X3Cursor c2;
   c2.seg = (int)(s0 / J.sps);
   c2.k = (int)((s0 - (int64_t)c2.seg * J.sps) * BK);
@@ -148,28 +141,31 @@ __device__ __forceinline__ void x3_loop(const FactorJobDev& J, const float* cons
   // registers reloaded with stage s0 + 1
   const int k0 = c2.k, seg0 = c2.seg;
 #pragma unroll
-  for (int f = 0; f < 4; ++f)
-    if (USE[f]) ld8(f, c2, x[f]);
+  for (int f = 0; f < NP; ++f) ld8(f, c2, x[f]);
   advance(c2);
-  X3Cursor c1 = c2;  // (fragments 1 / 3 load stage s0 + 1 in the first stage)
+  X3Cursor c1 = c2;  // (fragments 2 / 3 load stage s0 + 1 in the first stage)
   int kc = k0, kcs = seg0;  // first row and batch of the stage being multiplied
-  auto fix = [&](int f, int kstage, int kseg) {  // the ones column: 1 on the batch's rows, 0 past them
-    if constexpr (FILL) {
-      const int nvalid = (int)seg_rows(J, kseg) - kstage;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) x[f][r] = onesl[f] ? (lr + r < nvalid ? 1.f : 0.f) : x[f][r];
-    }
-  };
   // split fragment f (of the stage starting at row kstage of batch kseg) and reload its
-  // registers
+  // registers.  The ones column (FILL) loads as zeros (past the record limit), so its
+  // lane's split is zero and its ones -- on the batch's rows, none past them -- are set
+  // in the high parts: bf16 1.0 per valid row (on the fp32 values before the split: 8
+  // more registers).  A clique's panels ascend and the ones column is in the factor's
+  // last panel: only its last slot can hold it.
   auto take = [&](int f, int kstage, int kseg, const X3Cursor& c) {
-    fix(f, kstage, kseg);
-    const X3Frag fr = x3_split8(x[f]);
+    X3Frag fr = x3_split8(x[f]);
+    if (FILL && (DIAG || f == NP - 1)) {
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+      const int nv = onesl[f] ? (int)seg_rows(J, kseg) - kstage - lr : 0;  // the lane's valid rows
+      u32x4 h = __builtin_bit_cast(u32x4, fr.p[0]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) h[i] |= (nv > 2 * i ? 0x3f80u : 0u) | (nv > 2 * i + 1 ? 0x3f800000u : 0u);
+      fr.p[0] = __builtin_bit_cast(bf16x8, h);
+    }
     ld8(f, c, x[f]);
     return fr;
   };
   X3Frag pa = take(0, k0, seg0, c2);
-  X3Frag pb = SAME ? pa : take(2, k0, seg0, c2);
+  X3Frag pb = take(1, k0, seg0, c2);
   // the prologue's loads complete here (once per task): the loop header then starts
   // from a precise wait state, and the compiler keeps the counted vmcnt at the top of
   // each stage (with the prologue's loads still in flight it merged them into a
@@ -177,82 +173,68 @@ __device__ __forceinline__ void x3_loop(const FactorJobDev& J, const float* cons
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // (6 / 11 VALU slots per MFMA measured equal within the box's +-4 us, profiles/r04v/)
   constexpr int NV = FILL ? 52 / 6 + 1 : 44 / 6 + 1;
-  // one stage: P = (A0, B0) of this stage in, (A0', B0') of the next stage out
-  auto stage = [&](const X3Frag& A0, const X3Frag& B0, X3Frag& A0n, X3Frag& B0n) {
-    const int kn = c2.k, kns = c2.seg;  // first row / batch of the next stage (in x0 / x2 now)
-    // the cursors: x1 / x3 reload the next stage, x0 / x2 the one after
+  // one stage: (F0, F1) of this stage in, (F0', F1') of the next stage out
+  auto stage = [&](const X3Frag& F0, const X3Frag& F1, X3Frag& F0n, X3Frag& F1n) {
+    const int kn = c2.k, kns = c2.seg;  // first row / batch of the next stage (in x0 / x1 now)
+    // the cursors: x2 / x3 reload the next stage, x0 / x1 the one after
     c1 = c2;
     advance(c2);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (PAIR) {  // B0 = C0
-      const X3Frag A1 = take(1, kc, kcs, c1);
-      x3_six(acc[0][0], A0, A0);
+    if constexpr (DIAG) {
+      const X3Frag F2 = take(2, kc, kcs, c1);
+      x3_six(acc[0], F0, F0);
       x3_pattern<NV>();
       __builtin_amdgcn_sched_barrier(0);
-      A0n = take(0, kn, kns, c2);
-      x3_six(acc[0][1], B0, A0);
+      const X3Frag F3 = take(3, kc, kcs, c1);
+      x3_six(acc[1], F1, F1);
       x3_pattern<NV>();
       __builtin_amdgcn_sched_barrier(0);
-      B0n = take(2, kn, kns, c2);
-      x3_six(acc[1][0], A1, A0);
+      F0n = take(0, kn, kns, c2);
+      x3_six(acc[2], F2, F2);
       x3_pattern<NV>();
       __builtin_amdgcn_sched_barrier(0);
-      x3_six(acc[1][1], A1, A1);
+      F1n = take(1, kn, kns, c2);
+      x3_six(acc[3], F3, F3);
+      x3_pattern<NV>();
+    } else if constexpr (NP == 4) {
+      const X3Frag F2 = take(2, kc, kcs, c1);
+      x3_six(acc[0], F1, F0);
+      x3_pattern<NV>();
+      __builtin_amdgcn_sched_barrier(0);
+      const X3Frag F3 = take(3, kc, kcs, c1);
+      x3_six(acc[1], F2, F0);
+      x3_pattern<NV>();
+      __builtin_amdgcn_sched_barrier(0);
+      x3_six(acc[3], F3, F0);
       x3_pattern<0>();
       __builtin_amdgcn_sched_barrier(0);
-      x3_six(acc4, B0, A1);
+      F0n = take(0, kn, kns, c2);
+      x3_six(acc[2], F2, F1);
+      x3_pattern<NV>();
+      __builtin_amdgcn_sched_barrier(0);
+      x3_six(acc[4], F3, F1);
       x3_pattern<0>();
-    } else if constexpr (MASK == 15) {
-      const X3Frag A1 = take(1, kc, kcs, c1);
-      x3_six(acc[0][0], A0, B0);
+      __builtin_amdgcn_sched_barrier(0);
+      F1n = take(1, kn, kns, c2);
+      x3_six(acc[5], F3, F2);
+      x3_pattern<NV>();
+    } else if constexpr (NP == 3) {
+      const X3Frag F2 = take(2, kc, kcs, c1);
+      x3_six(acc[0], F1, F0);
       x3_pattern<NV>();
       __builtin_amdgcn_sched_barrier(0);
-      const X3Frag B1 = take(3, kc, kcs, c1);
-      x3_six(acc[1][0], A1, B0);
+      F0n = take(0, kn, kns, c2);
+      x3_six(acc[1], F2, F0);
       x3_pattern<NV>();
       __builtin_amdgcn_sched_barrier(0);
-      A0n = take(0, kn, kns, c2);
-      x3_six(acc[0][1], A0, B1);
+      F1n = take(1, kn, kns, c2);
+      x3_six(acc[2], F2, F1);
       x3_pattern<NV>();
-      __builtin_amdgcn_sched_barrier(0);
-      B0n = take(2, kn, kns, c2);
-      x3_six(acc[1][1], A1, B1);
-      x3_pattern<NV>();
-    } else if constexpr (MASK == 13) {  // diagonal: (0,0) (1,0) (1,1), B = A
-      const X3Frag A1 = take(1, kc, kcs, c1);
-      x3_six(acc[0][0], A0, A0);
-      x3_pattern<NV>();
-      __builtin_amdgcn_sched_barrier(0);
-      x3_six(acc[1][0], A1, A0);
-      A0n = take(0, kn, kns, c2);
-      x3_pattern<NV>();
-      __builtin_amdgcn_sched_barrier(0);
-      x3_six(acc[1][1], A1, A1);
-      x3_pattern<0>();
-      B0n = A0n;
-    } else if constexpr (MASK == 5) {  // (0,0) (1,0)
-      const X3Frag A1 = take(1, kc, kcs, c1);
-      x3_six(acc[0][0], A0, B0);
-      x3_pattern<NV>();
-      __builtin_amdgcn_sched_barrier(0);
-      A0n = take(0, kn, kns, c2);
-      B0n = take(2, kn, kns, c2);
-      x3_six(acc[1][0], A1, B0);
+    } else {  // a single block (1, 0)
+      F0n = take(0, kn, kns, c2);
+      F1n = take(1, kn, kns, c2);
+      x3_six(acc[0], F1, F0);
       x3_pattern<2 * NV>();
-    } else if constexpr (MASK == 3) {  // (0,0) (0,1): the last tile row of a factor
-      const X3Frag B1 = take(3, kc, kcs, c1);
-      x3_six(acc[0][0], A0, B0);
-      x3_pattern<NV>();
-      __builtin_amdgcn_sched_barrier(0);
-      A0n = take(0, kn, kns, c2);
-      B0n = take(2, kn, kns, c2);
-      x3_six(acc[0][1], A0, B1);
-      x3_pattern<2 * NV>();
-    } else {  // 1: the last diagonal tile, (0,0) only, B = A
-      A0n = take(0, kn, kns, c2);
-      x3_six(acc[0][0], A0, A0);
-      x3_pattern<NV>();
-      B0n = A0n;
     }
     kc = kn;
     kcs = kns;
@@ -262,199 +244,97 @@ __device__ __forceinline__ void x3_loop(const FactorJobDev& J, const float* cons
   const int64_t rst = J.rstage;
   const int bst = (rst > s0 && rst < s1) ? (int)(rst - s0) : -1;
   for (int st = 0; st < ns; ++st) {
-    if (st == bst) {
-      scale_acc(acc[0], J.rinv);
-      scale_acc(acc[1], J.rinv);
-      if constexpr (PAIR) {
-        floatx16 a4[1] = {acc4};
-        scale_acc(a4, J.rinv);
-        acc4 = a4[0];
-      }
-    }
+    if (st == bst) scale_acc(acc, J.rinv);
     X3Frag qa, qb;
     stage(pa, pb, qa, qb);
     pa = qa;
     pb = qb;
   }
-  if (rst >= 0 && s1 > rst) {
-    scale_acc(acc[0], J.rw);
-    scale_acc(acc[1], J.rw);
-    if constexpr (PAIR) {
-      floatx16 a4[1] = {acc4};
-      scale_acc(a4, J.rw);
-      acc4 = a4[0];
-    }
+  if (rst >= 0 && s1 > rst) scale_acc(acc, J.rw);
+}
+
+// One unit of kind KIND: its accumulators, the stage loop and the two waves' hand-off.
+// The unit's blocks, in accumulator order: block b is (row panel pr, column panel pc),
+// sub-block (pr & 1, pc & 1) of 64 x 64 tile (pr >> 1, pc >> 1) of the job's slabs.
+// Wave 0 stores the first half of them and wave 1 the rest: each hands the other's
+// partials through LDS slot b ([16 values][64 lanes]), then adds the other wave's to
+// its own.  Both sums are w0 + w1 (IEEE addition commutes): deterministic.
+// (One function per kind, accumulators and all: with one accumulator set shared by the
+// kinds' loops the kernel compiled to 251 VGPRs, each kind alone to 187-205.)
+template <int KIND>
+__device__ __forceinline__ void x3_unit(const FactorJobDev& J, const float* const* segs, const int (&pn)[4],
+                                        int np, int split, float* lds) {
+  constexpr bool DIAG = KIND == X3_KDIAG;
+  constexpr int NB = x3_kind_blocks(KIND);
+  const int64_t s0 = (int64_t)split * J.chunk;
+  const int64_t s1 = min(J.nst, s0 + J.chunk);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  floatx16 acc[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[b][v] = 0.f;
+  if (s1 > s0) {
+    // FILL: one of the unit's fragments holds the ones column (the last panel of an A
+    // factor with a bias)
+    const int op = J.x.ones >> 5;
+    const bool fill = J.x.ones >= 0 && (pn[0] == op || pn[1] == op || pn[2] == op || pn[3] == op);
+    if (fill) x3_loop<KIND, true>(J, segs, pn, s0, s1, acc);
+    else x3_loop<KIND, false>(J, segs, pn, s0, s1, acc);
+  }
+  const int nblk = DIAG ? np : NB;  // (a diagonal unit of fewer than four panels)
+  constexpr int HALF = (NB + 1) / 2;
+  __syncthreads();
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    const bool mine = (b < HALF) == (wave == 0);
+    if (b < nblk && !mine)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) lds[(b * 16 + v) * 64 + lane] = acc[b][v];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    const bool mine = (b < HALF) == (wave == 0);
+    if (b >= nblk || !mine) continue;
+    // (slot of the block's row / column panel, by the accumulator order above)
+    constexpr int BI[6] = {1, 2, 2, 3, 3, 3}, BJ[6] = {0, 0, 1, 0, 1, 2};
+    const int pr = DIAG ? pn[b & 3] : pn[BI[b]], pc = DIAG ? pn[b & 3] : pn[BJ[b]];
+    const int ti = pr >> 1, tj = pc >> 1;
+    float* out = J.slab + ((size_t)(ti * (ti + 1) / 2 + tj) * J.sstride + split) * TILE * TILE +
+                 (pr & 1) * 32 * TILE + (pc & 1) * 32;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[b][v] += lds[(b * 16 + v) * 64 + lane];
+    put_partial(J, acc[b], [&](int v) { return &out[acc_row(v, lane) * TILE + (lane & 31)]; });
   }
 }
 
-template <int GBK, int NSLOT>
-__device__ __forceinline__ void factor_task_x3(const FactorJobDev& J, const float* const* segs, int local,
-                                               float* lds, int split_major) {
+template <int GBK>
+__device__ __forceinline__ void factor_task_x3(const FactorJobDev& J, const float* const* segs,
+                                               const X3Units& U, int local, float* lds, int split_major) {
   static_assert(GBK == 16 * X3_NW, "one 16-row half stage per wave");
-  const int T = J.t;
-  const bool thin = J.x3pair != 0;
-  const int units = x3_units_of(T, thin);
-  const int sf = J.splits - J.xsplits;  // the full K-splits (every unit)
-  int split, unit;
-  if (local >= units * sf) {  // the pair units' extra K-splits (x3_xsplits)
-    const int e = local - units * sf;
-    split = sf + e / (T - 1);
-    unit = e - (split - sf) * (T - 1);
-  } else {
-    split = split_major ? local / units : local % sf;
-    unit = split_major ? local - split * units : local / sf;
+  const int units = J.x3units;
+  const int split = split_major ? local / units : local % J.splits;
+  const int unit = split_major ? local - split * units : local / J.splits;
+  const uint32_t u = U.u[J.x3tab + unit];
+  const int np = x3_unit_np(u);
+  const int pn[4] = {x3_unit_panel(u, 0), x3_unit_panel(u, 1), x3_unit_panel(u, 2), x3_unit_panel(u, 3)};
+  switch ((u & X3_DIAG) ? X3_KDIAG : np) {
+    case 4: x3_unit<4>(J, segs, pn, np, split, lds); break;
+    case 3: x3_unit<3>(J, segs, pn, np, split, lds); break;
+    case 2: x3_unit<2>(J, segs, pn, np, split, lds); break;
+    case X3_KDIAG: x3_unit<X3_KDIAG>(J, segs, pn, np, split, lds); break;
+    default: break;  // (not reached)
   }
-  int ti, tj;
-  bool pair = false;
-  if (!thin) {
-    tri_decode(unit, ti, tj);
-  } else if (unit < T - 1) {  // pairs first: diagonal (i, i) with edge (T-1, i)
-    pair = true;
-    ti = unit;
-    tj = T - 1;
-  } else if (unit < T - 1 + (T - 1) * (T - 2) / 2) {  // strictly lower tiles of rows < T-1
-    tri_decode(unit - (T - 1), ti, tj);
-    ++ti;  // (row i of the strict lower triangle has i tiles: tri index of (i-1, j))
-  } else {  // the corner (T-1, T-1)
-    ti = tj = T - 1;
-  }
-  const int tile = ti * (ti + 1) / 2 + (pair ? ti : tj);  // (a pair's: its diagonal tile)
-  // a pair unit's K-chunk: nst over all `splits` slabs; the others' over the full splits
-  const int64_t chunk = pair && J.xsplits ? (J.nst + J.splits - 1) / J.splits : J.chunk;
-  const int64_t s0 = (int64_t)split * chunk;
-  const int64_t s1 = min(J.nst, s0 + chunk);
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const bool same = ti == tj;
-  bool act[2][2];
-  int mask = 0;
-#pragma unroll
-  for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj) {
-      act[bi][bj] = !(same && bi < bj) && ti * TILE + bi * 32 < J.n && tj * TILE + bj * 32 < J.n;
-      mask |= act[bi][bj] << (2 * bi + bj);
-    }
-  if (pair) mask = X3_PAIR;
-  floatx16 acc[2][2], acc4;
-#pragma unroll
-  for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[bi][bj][v] = 0.f;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) acc4[v] = 0.f;
-  if (s1 > s0) {
-    // FILL: one of the task's fragments holds the ones column (the last tile row /
-    // column of an A factor with a bias)
-    const bool fill = J.x.ones >= 0 && ((J.x.ones >> 6) == ti || (J.x.ones >> 6) == tj);
-#define X3_CASE(M)                                                   \
-  case M:                                                            \
-    if (fill) x3_loop<M, true>(J, segs, ti, tj, s0, s1, acc, acc4);  \
-    else x3_loop<M, false>(J, segs, ti, tj, s0, s1, acc, acc4);      \
-    break;
-    switch (mask) {  // (block (0, 0) always has work)
-      X3_CASE(X3_PAIR)
-      X3_CASE(15)
-      X3_CASE(13)  // diagonal
-      X3_CASE(5)
-      X3_CASE(3)
-      X3_CASE(1)
-      default: break;  // (not reached)
-    }
-#undef X3_CASE
-  }
-  if (pair) {
-    // wave 0 keeps D00, E00, E01 and wave 1 D10, D11; each hands the other's through
-    // LDS slots [D00, D10, D11, E00, E01][16 values][64 lanes]; sums are w0 + w1
-    __syncthreads();
-    float* xo = lds;
-    auto put = [&](int sl, const floatx16& a) {
-#pragma unroll
-      for (int v = 0; v < 16; ++v) xo[(sl * 16 + v) * 64 + lane] = a[v];
-    };
-    auto add = [&](int sl, floatx16& a) {
-#pragma unroll
-      for (int v = 0; v < 16; ++v) a[v] += xo[(sl * 16 + v) * 64 + lane];
-    };
-    float* outD = J.slab + ((size_t)tile * J.sstride + split) * TILE * TILE;
-    float* outE = J.slab + ((size_t)((T - 1) * T / 2 + ti) * J.sstride + split) * TILE * TILE;
-    auto store = [&](float* o, int bi, int bj, const floatx16& a) {
-      put_partial(J, a, [&](int v) { return &o[(bi * 32 + acc_row(v, lane)) * TILE + bj * 32 + (lane & 31)]; });
-    };
-    if (wave == 0) {
-      put(1, acc[1][0]);
-      put(2, acc[1][1]);
-    } else {
-      put(0, acc[0][0]);
-      put(3, acc[0][1]);
-      put(4, acc4);
-    }
-    __syncthreads();
-    if (wave == 0) {
-      add(0, acc[0][0]);
-      add(3, acc[0][1]);
-      add(4, acc4);
-      store(outD, 0, 0, acc[0][0]);
-      store(outE, 0, 0, acc[0][1]);
-      store(outE, 0, 1, acc4);
-    } else {
-      add(1, acc[1][0]);
-      add(2, acc[1][1]);
-      store(outD, 1, 0, acc[1][0]);
-      store(outD, 1, 1, acc[1][1]);
-    }
-    return;
-  }
-  // wave w stores block row w: it hands the other block row's partials to the other
-  // wave through LDS (the ring is free after the barrier), then adds the other
-  // wave's.  Both sums are w0 + w1 (IEEE addition commutes): deterministic.
-  __syncthreads();
-  float* xo = lds;  // [wave][bj][16 values][64 lanes]
-  float* out = J.slab + ((size_t)tile * J.sstride + split) * TILE * TILE;
-  auto hand = [&](auto bic) {
-    constexpr int bi = decltype(bic)::value;
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj)
-      if (act[bi][bj])
-#pragma unroll
-        for (int v = 0; v < 16; ++v) xo[((wave * 2 + bj) * 16 + v) * 64 + lane] = acc[bi][bj][v];
-  };
-  auto keep = [&](auto bic) {
-    constexpr int bi = decltype(bic)::value;
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj)
-      if (act[bi][bj]) {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) acc[bi][bj][v] += xo[(((1 - wave) * 2 + bj) * 16 + v) * 64 + lane];
-        put_partial(J, acc[bi][bj],
-                    [&](int v) { return &out[(bi * 32 + acc_row(v, lane)) * TILE + bj * 32 + (lane & 31)]; });
-        // the slabs of the pair units' extra K-splits hold nothing of this tile: its
-        // last full K-split writes them as zero partials
-        if (split == sf - 1)
-          for (int x = 1; x <= J.xsplits; ++x) {
-            floatx16 z;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) z[v] = 0.f;
-            float* o = out + (size_t)x * TILE * TILE;
-            put_partial(J, z, [&](int v) { return &o[(bi * 32 + acc_row(v, lane)) * TILE + bj * 32 + (lane & 31)]; });
-          }
-      }
-  };
-  if (wave == 0) hand(std::integral_constant<int, 1>{});
-  else hand(std::integral_constant<int, 0>{});
-  __syncthreads();
-  if (wave == 0) keep(std::integral_constant<int, 0>{});
-  else keep(std::integral_constant<int, 1>{});
 }
 
 // Every job of the launch is LDS-DMA-eligible or narrow (n <= 32: direct loads).
-// 2 waves per SIMD (178 VGPRs): 4 workgroups per CU leave a 32-tile inversion
-// workgroup (107 registers, 29 KB) room to run beside the pass
-__global__ __launch_bounds__(X3_THREADS, 2) void kfac_factor_tiles_x3(FactorArgs args) {
-  // (LDS only for the epilogue's hand-off: a block row, 16 KB; a pair's blocks, 20 KB)
-  __shared__ __attribute__((aligned(16))) float lds[5 * 16 * 64];
+// 2 waves per SIMD: 4 workgroups per CU leave a 32-tile inversion workgroup (107
+// registers, 29 KB) room to run beside the pass
+__global__ __launch_bounds__(X3_THREADS, 2) void kfac_factor_tiles_x3(FactorArgs args, X3Units units) {
+  // (LDS only for the epilogue's hand-off: a K4's six blocks, 24 KB)
+  __shared__ __attribute__((aligned(16))) float lds[X3_NACC * 16 * 64];
   // (no start stagger here: the fp32 kernel's +2.5 % measured neutral on this one, MLP
   // line 1.951-1.954e8 without vs 1.951-1.957e8 with, 3 alternating runs, profiles/r06b/)
   const int task = xcd_task(blockIdx.x, gridDim.x);
@@ -465,13 +345,151 @@ __global__ __launch_bounds__(X3_THREADS, 2) void kfac_factor_tiles_x3(FactorArgs
   if (J.n <= 32)
     factor_task_narrow_direct<X3_NW>(J, args.segs, local, lds);
   else
-    factor_task_x3<BK, 2>(J, args.segs, local, lds, args.split_major);
+    factor_task_x3<BK>(J, args.segs, units, local, lds, args.split_major);
 }
 
 // ------------------------------------------------------------------- host side
+namespace {
+
+uint32_t x3_pack(const int* p, int np, bool diag) {
+  uint32_t u = (uint32_t)np << 24 | (diag ? X3_DIAG : 0u);
+  for (int s = 0; s < 4; ++s) u |= (uint32_t)p[std::min(s, np - 1)] << (6 * s);
+  return u;
+}
+
+// The table of P panels.  P = 25: the 25 translates of two base blocks of the affine plane
+// coordinates (x, y) of Z5 x Z5, panel 5 x + y -- {(0,0), (0,1), (1,0), (2,2)} and twice
+// it; their 24 differences are the 24 non-zero vectors, each once, so every panel pair
+// lies in exactly one of the 50 blocks (a Steiner system S(2, 4, 25)).  Any other P: the
+// first K4 in lexicographic order whose six pairs are all free, until none is left, then
+// K3s and K2s the same way; a pair is never taken twice, and the K2 pass takes every pair
+// still free, so the partition is exact whatever the packing's quality.
+std::vector<uint32_t> x3_build_table(int P) {
+  std::vector<uint32_t> k4, k3, k2, dg;
+  std::vector<char> used((size_t)P * P, 0);
+  auto is_free = [&](int a, int b) { return !used[(size_t)a * P + b]; };
+  auto mark = [&](int a, int b) { used[(size_t)a * P + b] = used[(size_t)b * P + a] = 1; };
+  if (P == 25) {
+    const int base[4][2] = {{0, 0}, {0, 1}, {1, 0}, {2, 2}};
+    for (int m = 1; m <= 2; ++m)
+      for (int sx = 0; sx < 5; ++sx)
+        for (int sy = 0; sy < 5; ++sy) {
+          int p[4];
+          for (int i = 0; i < 4; ++i) p[i] = 5 * ((m * base[i][0] + sx) % 5) + (m * base[i][1] + sy) % 5;
+          std::sort(p, p + 4);
+          for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < i; ++j) mark(p[i], p[j]);
+          k4.push_back(x3_pack(p, 4, false));
+        }
+  }
+  for (int a = 0; a < P; ++a)
+    for (int b = a + 1; b < P; ++b) {
+      if (!is_free(a, b)) continue;
+      for (int c = b + 1; c < P && is_free(a, b); ++c) {
+        if (!is_free(a, c) || !is_free(b, c)) continue;
+        for (int d = c + 1; d < P; ++d)
+          if (is_free(a, d) && is_free(b, d) && is_free(c, d)) {
+            const int p[4] = {a, b, c, d};
+            for (int i = 0; i < 4; ++i)
+              for (int j = 0; j < i; ++j) mark(p[i], p[j]);
+            k4.push_back(x3_pack(p, 4, false));
+            break;
+          }
+      }
+    }
+  for (int a = 0; a < P; ++a)
+    for (int b = a + 1; b < P; ++b)
+      for (int c = b + 1; c < P && is_free(a, b); ++c)
+        if (is_free(a, c) && is_free(b, c)) {
+          const int p[3] = {a, b, c};
+          mark(a, b), mark(a, c), mark(b, c);
+          k3.push_back(x3_pack(p, 3, false));
+        }
+  for (int a = 0; a < P; ++a)
+    for (int b = a + 1; b < P; ++b)
+      if (is_free(a, b)) {
+        const int p[2] = {a, b};
+        mark(a, b);
+        k2.push_back(x3_pack(p, 2, false));
+      }
+  for (int a = 0; a < P; a += 4) {
+    int p[4], np = 0;
+    for (; np < 4 && a + np < P; ++np) p[np] = a + np;
+    dg.push_back(x3_pack(p, np, true));
+  }
+  std::vector<uint32_t> t(k4);
+  t.insert(t.end(), dg.begin(), dg.end());
+  t.insert(t.end(), k3.begin(), k3.end());
+  t.insert(t.end(), k2.begin(), k2.end());
+  return t;
+}
+
+}  // namespace
+
+int x3_unit_table(int P, const uint32_t** table) {
+  static std::mutex mu;
+  static std::vector<uint32_t> tables[X3_PMAX + 1];
+  if (P < 2 || P > X3_PMAX) return 0;
+  std::lock_guard<std::mutex> lock(mu);
+  if (tables[P].empty()) tables[P] = x3_build_table(P);
+  if (table) *table = tables[P].data();
+  return (int)tables[P].size();
+}
+
+int x3_units(int n) { return n <= 32 ? 1 : x3_unit_table(x3_panels(n), nullptr); }
+
+int x3_table_entries(const int* n, int njobs) {
+  bool seen[X3_PMAX + 1] = {};
+  int total = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const int P = x3_panels(n[i]);
+    if (n[i] <= 32 || P > X3_PMAX || seen[P]) continue;
+    seen[P] = true;
+    total += x3_unit_table(P, nullptr);
+  }
+  return total;
+}
+
+// The launch's unit tables go with the kernel arguments: one copy per distinct P, each
+// job pointed at its own (x3tab; the router keeps a group within X3_UCAP entries).
 int launch_tiles_x3(const FactorArgs& args, int tasks, hipStream_t stream) {
-  hipLaunchKernelGGL(kfac_factor_tiles_x3, dim3(tasks), dim3(X3_THREADS), 0, stream, args);
+  FactorArgs a = args;
+  X3Units U;
+  int off[X3_PMAX + 1], total = 0;
+  std::fill(off, off + X3_PMAX + 1, -1);
+  for (int i = 0; i < a.njobs; ++i) {
+    FactorJobDev& d = a.job[i];
+    d.x3tab = 0;
+    if (d.n <= 32) continue;
+    const int P = x3_panels(d.n);
+    const uint32_t* t = nullptr;
+    const int nu = x3_unit_table(P, &t);
+    if (nu == 0 || nu != d.x3units) return KFAC_ELAUNCH;
+    if (off[P] < 0) {
+      if (total + nu > X3_UCAP) return KFAC_ELAUNCH;
+      std::copy(t, t + nu, U.u + total);
+      off[P] = total;
+      total += nu;
+    }
+    d.x3tab = off[P];
+  }
+  std::fill(U.u + total, U.u + X3_UCAP, 0u);
+  hipLaunchKernelGGL(kfac_factor_tiles_x3, dim3(tasks), dim3(X3_THREADS), 0, stream, a, U);
   return KFAC_OK;
 }
 
 }  // namespace kfac
+
+// The unit table of P panels, unpacked for inspection (include/kfac_hip.h)
+extern "C" int kfac_x3_unit_table(int P, int32_t* out, int cap) {
+  const uint32_t* t = nullptr;
+  const int nu = kfac::x3_unit_table(P, &t);
+  for (int i = 0; i < nu && i < cap && out; ++i) {
+    const int np = kfac::x3_unit_np(t[i]);
+    const bool diag = (t[i] & kfac::X3_DIAG) != 0;
+    for (int s = 0; s < 4; ++s) out[6 * i + s] = s < np ? kfac::x3_unit_panel(t[i], s) : -1;
+    out[6 * i + 4] = diag ? 0 : (np == 4 ? 63 : np == 3 ? 0b001011 : 0b000001);
+    out[6 * i + 5] = diag ? (1 << np) - 1 : 0;
+  }
+  return nu;
+}

@@ -129,6 +129,14 @@ KFAC_API int kfac_factor_accum_plan(const kfac_factor_job* jobs, int njobs, int3
  * step of kfac_factor_update, deferred (x is only read for the factor size). */
 KFAC_API int kfac_factor_flush(const kfac_factor_job* jobs, int njobs, kfac_stream_t stream);
 
+/* kfac_factor_tiles_x3's work units of a factor of P 32-column panels (2 <= P <= 64), for
+ * inspection; no GPU needed.  Unit i in out[6 i .. 6 i + 5]: its up to four panels
+ * a < b < c < d (-1: none), the 6-bit mask of the panel pairs (32 x 32 blocks) it owns --
+ * bit 0 (b, a), 1 (c, a), 2 (d, a), 3 (c, b), 4 (d, b), 5 (d, c) -- and the 4-bit mask of the
+ * panels whose diagonal block it owns.  Fills at most cap units; returns the number of
+ * units of the table (0: P out of range).                                           */
+KFAC_API int kfac_x3_unit_table(int P, int32_t* out, int cap);
+
 /* Single-factor conveniences (same kernels). */
 KFAC_API int kfac_syrk_linear(const float* x, int64_t B, int64_t d, int64_t ldx, int has_ones,
                      float alpha, float beta, float* F, int64_t ldF, void* workspace,
