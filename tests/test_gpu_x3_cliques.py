@@ -18,7 +18,8 @@ that weight gives integers too (1.6 x 25 m = 40 m, 1.6 x 5 m = 8 m against the o
 64 for the ones' own sum), the kernel's 0.625 rescale of the earlier batches is a division by 8
 of a multiple of 5, and a product with float32(1.6) = 1.6 (1 + 1.5e-8) rounds to the integer
 below 2^23.  The same shapes with U[0, 1) and N(0, 1) inputs are held against fp64 at
-|err| <= 1e-5 max|F|."""
+|err| <= 1e-5 max|F|.  (Integers bind the geometry through hi hi alone; test_gpu_x3_term_exact.py
+binds the mid and lo products.)"""
 import numpy as np
 import pytest
 import torch
