@@ -980,12 +980,16 @@ static int tridiag_eig(const kfac_eig_job& j, char* ws, int32_t* info, hipStream
 
 extern "C" size_t kfac_eig_workspace_bytes(const kfac_eig_job* jobs, int njobs) {
   if (!jobs || njobs <= 0) return 0;
-  // small factors run grouped (V per job); large ones one at a time (stream-ordered reuse)
+  // small factors run grouped (V per job); large ones one at a time (stream-ordered reuse).
+  // The groups are kfac_syev's: a large job closes the pending small group, as does the
+  // EMAXJ-th small job
   size_t best = 0, tot = 0;
   int in_group = 0;
   for (int i = 0; i < njobs; ++i) {
     if (jobs[i].n > EIG_LDS_MAX) {
-      best = std::max(best, tri_plan(jobs[i].n, jobs[i].evecs != nullptr).ws);
+      best = std::max({best, tot, tri_plan(jobs[i].n, jobs[i].evecs != nullptr).ws});
+      tot = 0;
+      in_group = 0;
       continue;
     }
     if (in_group == EMAXJ) { best = std::max(best, tot); tot = 0; in_group = 0; }
