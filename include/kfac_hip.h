@@ -157,7 +157,13 @@ KFAC_API int kfac_syrk_convgrad(const float* g, int64_t B, int C, int64_t L, flo
  * (models/curvatures.py:367-398); the regression block passes scale = N,
  * shift = N*tau with KFAC_OUT_INVERSE (regression_ll_block.py:130-133).
  * info[j] (device) = 0, or the 1-based index of the first non-positive pivot
- * of job j (the reference's RuntimeError / LinAlgError condition).          */
+ * of job j (the reference's RuntimeError / LinAlgError condition).  Pivots are
+ * counted in the elimination's own order, that of the flipped matrix P R P:
+ * pivot p belongs to row n - p + 1 of F, counted from 1 (a NaN pivot counts as
+ * non-positive).  Every call writes every info[j], 0 included; a failed job's
+ * `out` is unspecified, the other jobs of the call are not affected.
+ * `out` must not alias F (nor any other job's F): the launch that reads F
+ * already writes the zero blocks of `out`.                                    */
 enum kfac_inv_out { KFAC_OUT_INV_CHOL = 0, KFAC_OUT_INVERSE = 1 };
 
 typedef struct kfac_invert_job {
