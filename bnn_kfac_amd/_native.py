@@ -78,6 +78,19 @@ class CovOuterJob(ctypes.Structure):
                 ("K2", c_vp), ("ld2", c_i64), ("lower1", c_i32), ("lower2", c_i32)]
 
 
+class CovSweepJob(ctypes.Structure):
+    _fields_ = [("J", c_vp), ("ldJ", c_i64), ("nA", c_i32), ("nG", c_i32), ("VA", c_vp),
+                ("ldA", c_i64), ("VG", c_vp), ("ldG", c_i64), ("wA", c_vp), ("ldwA", c_i64),
+                ("wG", c_vp), ("ldwG", c_i64)]
+
+
+class CovOuterSweepJob(ctypes.Structure):
+    _fields_ = [("a", c_vp), ("lda", c_i64), ("cols", c_i32), ("has_ones", c_i32), ("D", c_vp),
+                ("ldD", c_i64), ("nG", c_i32), ("reserved", c_i32), ("VA", c_vp), ("ldA", c_i64),
+                ("VG", c_vp), ("ldG", c_i64), ("wA", c_vp), ("ldwA", c_i64), ("wG", c_vp),
+                ("ldwG", c_i64)]
+
+
 class SampleJob(ctypes.Structure):
     _fields_ = [("LA", c_vp), ("ldA", c_i64), ("LG", c_vp), ("ldG", c_i64), ("Z", c_vp),
                 ("nA", c_i32), ("nG", c_i32), ("W", c_vp), ("ldW", c_i64), ("bias", c_vp),
@@ -139,6 +152,16 @@ SIGNATURES = {
                                                               c_i64, ctypes.c_int]),
     "kfac_kron_cov_outer": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
                                            ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_kron_cov_sweep_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovSweepJob), ctypes.c_int,
+                                                              c_i64, ctypes.c_int, ctypes.c_int]),
+    "kfac_kron_cov_sweep": (ctypes.c_int, [ctypes.POINTER(CovSweepJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_kron_cov_outer_sweep_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovOuterSweepJob),
+                                                                    ctypes.c_int, c_i64, ctypes.c_int,
+                                                                    ctypes.c_int]),
+    "kfac_kron_cov_outer_sweep": (ctypes.c_int, [ctypes.POINTER(CovOuterSweepJob), ctypes.c_int, c_i64,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                                 ctypes.c_size_t, c_vp]),
     "kfac_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SampleJob), ctypes.c_int]),
     "kfac_sample": (ctypes.c_int, [ctypes.POINTER(SampleJob), ctypes.c_int, ctypes.c_int, c_vp,
                                    ctypes.c_size_t, c_vp]),
@@ -478,6 +501,35 @@ def kron_cov_outer(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool =
     ws = workspace.get(out.device, need)
     check(L.kfac_kron_cov_outer(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
                                 stream_handle(out.device)), "kfac_kron_cov_outer")
+
+
+def kron_cov_sweep_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
+    return lib().kfac_kron_cov_sweep_workspace_bytes(as_array(CovSweepJob, jobs), len(jobs), nb, nc, nt)
+
+
+def kron_cov_sweep(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_kron_cov_sweep: out (nt, nb, nc, nc) (+)= the weighted Grams, <= 8 jobs, nt <= 64."""
+    L = lib()
+    arr = as_array(CovSweepJob, jobs)
+    need = L.kfac_kron_cov_sweep_workspace_bytes(arr, len(jobs), nb, nc, nt)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_kron_cov_sweep(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws), ws.numel(),
+                                stream_handle(out.device)), "kfac_kron_cov_sweep")
+
+
+def kron_cov_outer_sweep_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
+    return lib().kfac_kron_cov_outer_sweep_workspace_bytes(as_array(CovOuterSweepJob, jobs), len(jobs),
+                                                           nb, nc, nt)
+
+
+def kron_cov_outer_sweep(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_kron_cov_outer_sweep: out (nt, nb, nc, nc) (+)= the weighted sums, <= 8 jobs, nt <= 64."""
+    L = lib()
+    arr = as_array(CovOuterSweepJob, jobs)
+    need = L.kfac_kron_cov_outer_sweep_workspace_bytes(arr, len(jobs), nb, nc, nt)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_kron_cov_outer_sweep(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws),
+                                      ws.numel(), stream_handle(out.device)), "kfac_kron_cov_outer_sweep")
 
 
 def sample(jobs, device: torch.device, accumulate: bool) -> None:

@@ -20,6 +20,11 @@
 // a0 the K-range [a0, nA)), and run in plain block order: the round-robin dispatch gives
 // every XCD the same mix.  Contiguous per-XCD ranges (xcd_task) put the long a-tiles on
 // XCD 0 and the short ones on XCD 7 and measured 1.5x slower; K1 fits any one L2.
+//
+// kfac_kron_cov_sweep (end of this file): the same covariance for up to 64 dampings at
+// once in the factors' eigenbasis.  apply runs once with K1 = V_A, K2 = V_G (dense); a
+// damping is a pair of weight vectors, and kfac_cov_sweep_gram / kfac_cov_sweep_reduce
+// form one weighted Gram per grid point from the staged rows (cov_wgram_segment).
 #include "covariance_common.h"
 
 namespace kfac {
@@ -186,6 +191,46 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_reduce(CovArgs args) {
   }
 }
 
+// Damping sweep (kfac_kron_cov_sweep): apply_u / apply_t above run once with K1 = V_A,
+// K2 = V_G (dense), so T_r = V_A^T M_r V_G; these two launches then weight it per tau.
+// Weighted Gram partials: rows c of sample b over one WSEG-long K segment, every tau;
+// partial is ntau x nb x nseg x nc*nc.
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_sweep_gram(CovArgs args, SweepArgs sw) {
+  __shared__ __attribute__((aligned(16))) float lds[WGRAM_LDS];
+  const int task = blockIdx.x;
+  const int j = cov_find_job(args.g_end, args.njobs, task);
+  const CovJobDev& C = args.job[j];
+  const int64_t local = task - C.g_begin;
+  const int64_t b = local / C.nseg;
+  const int seg = (int)(local % C.nseg);
+  const int nc = args.nc;
+  const int64_t K = (int64_t)C.nA * C.nG;
+  cov_wgram_segment<true>(C.T + b * nc * K, K, nc, (int64_t)seg * WSEG, sw.job[j], C.nG, sw.ntau,
+                          C.partial + local * nc * nc, args.nb * C.nseg * nc * nc, lds);
+}
+
+// cov[tau][b] (+)= kfac_cov_reduce's sum over tau's partials; grid (nb, ntau).
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_sweep_reduce(CovArgs args) {
+  const int64_t b = blockIdx.x, tau = blockIdx.y;
+  const int nc = args.nc, n2 = nc * nc;
+  float* cov = args.cov + (tau * args.nb + b) * n2;
+  for (int e = threadIdx.x; e < n2; e += NTHREADS) {
+    const int c = e / nc, c2 = e - c * nc;
+    if (c2 > c) continue;
+    double total = 0.0;
+    for (int j = 0; j < args.njobs; ++j) {
+      const CovJobDev& C = args.job[j];
+      const float* part = C.partial + (tau * args.nb + b) * C.nseg * n2 + e;
+      double s = 0.0;
+      for (int i = 0; i < C.nseg; ++i) s += (double)part[(int64_t)i * n2];
+      total += s;
+    }
+    const float v = args.accumulate ? (float)((double)cov[e] + total) : (float)total;
+    cov[e] = v;
+    cov[c2 * nc + c] = v;
+  }
+}
+
 static size_t cov_t_bytes(const kfac_cov_job& j, int64_t rows) {
   return align_up((size_t)rows * (size_t)j.nA * (size_t)j.nG * sizeof(float), 256);
 }
@@ -271,6 +316,97 @@ extern "C" int kfac_kron_cov(const kfac_cov_job* jobs, int njobs, int64_t nb, in
   hipLaunchKernelGGL(kfac_cov_gram, dim3((unsigned)ng), dim3(NTHREADS), 0, s, args);
   KFAC_CHECK_LAUNCH();
   hipLaunchKernelGGL(kfac_cov_reduce, dim3((unsigned)nb), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}
+
+// ------------------------------------------------------------------ damping sweep
+static int64_t sweep_nseg(const kfac_cov_sweep_job& j) { return cdiv((int64_t)j.nA * j.nG, WSEG); }
+static size_t sweep_t_bytes(const kfac_cov_sweep_job& j, int64_t rows) {
+  return align_up((size_t)rows * (size_t)j.nA * (size_t)j.nG * sizeof(float), 256);
+}
+static size_t sweep_partial_bytes(const kfac_cov_sweep_job& j, int64_t nb, int nc, int nt) {
+  return align_up((size_t)(nb * sweep_nseg(j)) * nc * nc * nt * sizeof(float), 256);
+}
+static bool sweep_job_ok(const kfac_cov_sweep_job& q) {
+  return q.J && q.VA && q.VG && q.wA && q.wG && q.nA > 0 && q.nG > 0 && q.ldA >= q.nA &&
+         q.ldG >= q.nG && q.ldwA >= q.nA && q.ldwG >= q.nG && q.ldJ >= (int64_t)q.nA * q.nG;
+}
+
+extern "C" size_t kfac_kron_cov_sweep_workspace_bytes(const kfac_cov_sweep_job* jobs, int njobs,
+                                                      int64_t nb, int nc, int nt) {
+  if (!jobs || njobs <= 0 || njobs > CMAXJ || nb <= 0 || nc <= 0 || nc > CMAXC || nt <= 0 ||
+      nt > SMAXT)
+    return 0;
+  size_t total = 0;
+  for (int i = 0; i < njobs; ++i) {
+    if (jobs[i].nA <= 0 || jobs[i].nG <= 0) return 0;
+    total += 2 * sweep_t_bytes(jobs[i], nb * nc) + sweep_partial_bytes(jobs[i], nb, nc, nt);
+  }
+  return total;
+}
+
+extern "C" int kfac_kron_cov_sweep(const kfac_cov_sweep_job* jobs, int njobs, int64_t nb, int nc,
+                                   int nt, int accumulate, float* cov, void* workspace,
+                                   size_t workspace_bytes, kfac_stream_t stream) {
+  if (!jobs || njobs <= 0 || njobs > CMAXJ || nb <= 0 || nc <= 0 || nc > CMAXC || nt <= 0 ||
+      nt > SMAXT || !cov)
+    return KFAC_EINVAL;
+  for (int i = 0; i < njobs; ++i)
+    if (!sweep_job_ok(jobs[i])) return KFAC_EINVAL;
+  const int64_t lim = (int64_t)1 << 31;
+  if (nb >= lim / nc) return KFAC_EINVAL;
+  const int64_t rows = nb * nc;
+  CovArgs args{};
+  SweepArgs sw{};
+  args.njobs = njobs;
+  args.nc = nc;
+  args.accumulate = accumulate;
+  args.nb = nb;
+  args.cov = cov;
+  sw.ntau = nt;
+  int64_t nu = 0, ntl = 0, ng = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const kfac_cov_sweep_job& q = jobs[i];
+    // (kfac_kron_cov's limits: 32-bit columns of the stacked operands, 32-bit task counts)
+    if (rows * q.nG >= lim - TILE || rows * q.nA >= lim - TILE) return KFAC_EINVAL;
+    CovJobDev& d = args.job[i];
+    d.J = q.J; d.K1 = q.VA; d.K2 = q.VG;
+    d.ldJ = q.ldJ; d.ld1 = q.ldA; d.ld2 = q.ldG;
+    d.nA = q.nA; d.nG = q.nG;
+    d.tg = (int)cdiv(q.nG, TILE);
+    d.nseg = (int)sweep_nseg(q);
+    d.lower1 = d.lower2 = 0;
+    d.ucols = (int)(rows * q.nG);
+    d.trows = (int)(rows * q.nA);
+    d.u_begin = (int)nu; d.t_begin = (int)ntl; d.g_begin = (int)ng;
+    nu += cdiv(q.nA, TILE) * cdiv(d.ucols, TILE);
+    ntl += cdiv(d.trows, TILE) * d.tg;
+    ng += nb * d.nseg;
+    if (nu >= lim || ntl >= lim || ng >= lim) return KFAC_EINVAL;
+    args.u_end[i] = (int)nu; args.t_end[i] = (int)ntl; args.g_end[i] = (int)ng;
+    sw.job[i].wA = q.wA; sw.job[i].wG = q.wG;
+    sw.job[i].ldwA = q.ldwA; sw.job[i].ldwG = q.ldwG;
+  }
+  if (!workspace || workspace_bytes < kfac_kron_cov_sweep_workspace_bytes(jobs, njobs, nb, nc, nt))
+    return KFAC_EWORKSPACE;
+  char* ws = (char*)workspace;
+  for (int i = 0; i < njobs; ++i) {
+    CovJobDev& d = args.job[i];
+    const size_t tb = sweep_t_bytes(jobs[i], rows);
+    d.U = reinterpret_cast<float*>(ws); ws += tb;
+    d.T = reinterpret_cast<float*>(ws); ws += tb;
+    d.partial = reinterpret_cast<float*>(ws); ws += sweep_partial_bytes(jobs[i], nb, nc, nt);
+  }
+  args.nu = (int)nu; args.nt = (int)ntl; args.ng = (int)ng;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kfac_cov_apply_u, dim3((unsigned)nu), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_apply_t, dim3((unsigned)ntl), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_sweep_gram, dim3((unsigned)ng), dim3(NTHREADS), 0, s, args, sw);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_sweep_reduce, dim3((unsigned)nb, (unsigned)nt), dim3(NTHREADS), 0, s, args);
   KFAC_CHECK_LAUNCH();
   return KFAC_OK;
 }

@@ -21,6 +21,11 @@
 // only, and every block is bitwise symmetric.
 // Rownorm tasks are ordered column-tile major, heaviest first, and run in plain block
 // order (covariance.hip's finding: per-XCD ranges put the long tiles on one XCD).
+//
+// kfac_kron_cov_outer_sweep (end of this file): up to 64 dampings at once in the factors'
+// eigenbasis.  The projections abar V_A and Delta V_G run once (K1 = V_A, K2 = V_G, dense);
+// kfac_cov_rownorm_w weights the squares per grid point in its epilogue, and
+// kfac_cov_outer_sweep_gram / _reduce form Q_b diag(wG) Q_b^T per grid point.
 #include "covariance_common.h"
 
 namespace kfac {
@@ -178,6 +183,112 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_reduce(OuterArgs args
   }
 }
 
+// ---- damping sweep (kfac_kron_cov_outer_sweep): K1 = V_A, K2 = V_G (dense), the
+// projections p = V_A^T abar and Q = Delta V_G once, then per grid point tau
+//   cov_tau[b] = sum_jobs (sum_i wA_tau[i] p_b[i]^2) * Q_b diag(wG_tau) Q_b^T .
+constexpr int RNTG = 16;  // grid points per cross-wave sum of the weighted row norm
+static_assert(SMAXT * TILE + RNTG * 4 * 32 <= 4 * PANEL, "weights + wave sums fit the staging buffer");
+
+// kfac_cov_rownorm's tile with a weighted epilogue: norm[tau][tile i][b] =
+// sum_{i in tile} wA_tau[i] * (abar_b V_A)[i]^2 for every tau, the tile's ntau x 64
+// weights staged in LDS (0 past nA); per tau the sums run in kfac_cov_rownorm's order.
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_rownorm_w(OuterArgs args, SweepArgs sw) {
+  __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
+  const int task = blockIdx.x;
+  const int jb = cov_find_job(args.n_end, args.njobs, task);
+  const OuterJobDev& C = args.job[jb];
+  const SweepWeights& W = sw.job[jb];
+  const int local = task - C.n_begin;
+  const int ti = local / C.bt;
+  const int i0 = ti * TILE, b0 = (local % C.bt) * TILE;
+  const OpDev k1 = rowmajor_op(C.K1, C.nA, C.nA, C.ld1);
+  const OpDev at = samplerows_op(C.a, C.cols, C.ones, (int)args.nb, C.lda);
+  floatx16 acc;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+  contract_tile<KFAC_ROWMAJOR, KFAC_SAMPLEROWS>(k1, i0, at, b0, 0, C.nA, false, true, lds, acc);
+  // (contract_tile leaves through a barrier: lds is free; columns i >= nA are zero)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ntau = sw.ntau;
+  float* red = lds + SMAXT * TILE;
+  for (int e = tid; e < ntau * TILE; e += NTHREADS) {
+    const int i = i0 + (e & (TILE - 1));
+    const float w = W.wA[(int64_t)(e >> 6) * W.ldwA + min(i, C.nA - 1)];
+    lds[e] = i < C.nA ? w : 0.f;
+  }
+  __syncthreads();
+  float sq[16];
+#pragma unroll
+  for (int v = 0; v < 16; ++v) sq[v] = acc[v] * acc[v];
+  const int wrow = (wave >> 1) * 32 + 4 * (lane >> 5);  // + acc_row's (v & 3) + 8 * (v >> 2)
+  for (int t0 = 0; t0 < ntau; t0 += RNTG) {
+    const int ng = min(RNTG, ntau - t0);
+    for (int t = 0; t < ng; ++t) {
+      const float* w = lds + (t0 + t) * TILE + wrow;
+      float s = 0.f;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) s += w[(v & 3) + 8 * (v >> 2)] * sq[v];
+      s += __shfl_xor(s, 32);
+      if (lane < 32) red[t * 128 + wave * 32 + lane] = s;
+    }
+    __syncthreads();
+    for (int e = tid; e < ng * TILE; e += NTHREADS) {
+      const int t = e >> 6, x = e & (TILE - 1), qj = x >> 5, j = x & 31;
+      const int64_t b = b0 + x;
+      // waves (qi, qj) = (0, qj) and (1, qj)
+      if (b < args.nb)
+        C.norm[((int64_t)(t0 + t) * C.at + ti) * args.nb + b] =
+            red[t * 128 + qj * 32 + j] + red[t * 128 + (2 + qj) * 32 + j];
+    }
+    __syncthreads();
+  }
+}
+
+// Weighted Gram partials of Q_b over one WSEG-long segment of nG, every tau.
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_sweep_gram(OuterArgs args, SweepArgs sw) {
+  __shared__ __attribute__((aligned(16))) float lds[WGRAM_LDS];
+  const int task = blockIdx.x;
+  const int jb = cov_find_job(args.g_end, args.njobs, task);
+  const OuterJobDev& C = args.job[jb];
+  const int64_t local = task - C.g_begin;
+  const int64_t b = local / C.nseg;
+  const int seg = (int)(local % C.nseg);
+  const int nc = args.nc;
+  const int64_t K = C.nG;
+  cov_wgram_segment<false>(C.V + b * nc * K, K, nc, (int64_t)seg * WSEG, sw.job[jb], C.nG, sw.ntau,
+                           C.partial + local * nc * nc, args.nb * C.nseg * nc * nc, lds);
+}
+
+// cov[tau][b] (+)= kfac_cov_outer_reduce's sum over tau's norms and partials; grid (nb, ntau).
+__global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_sweep_reduce(OuterArgs args) {
+  __shared__ double scale[CMAXJ];
+  const int64_t b = blockIdx.x, tau = blockIdx.y;
+  const int nc = args.nc, n2 = nc * nc;
+  if ((int)threadIdx.x < args.njobs) {
+    const OuterJobDev& C = args.job[threadIdx.x];
+    double s = 0.0;
+    for (int t = 0; t < C.at; ++t) s += (double)C.norm[(tau * C.at + t) * args.nb + b];
+    scale[threadIdx.x] = s;
+  }
+  __syncthreads();
+  float* cov = args.cov + (tau * args.nb + b) * n2;
+  for (int e = threadIdx.x; e < n2; e += NTHREADS) {
+    const int c = e / nc, c2 = e - c * nc;
+    if (c2 > c) continue;
+    double total = 0.0;
+    for (int j = 0; j < args.njobs; ++j) {
+      const OuterJobDev& C = args.job[j];
+      const float* part = C.partial + (tau * args.nb + b) * C.nseg * n2 + e;
+      double s = 0.0;
+      for (int i = 0; i < C.nseg; ++i) s += (double)part[(int64_t)i * n2];
+      total += scale[j] * s;
+    }
+    const float v = args.accumulate ? (float)((double)cov[e] + total) : (float)total;
+    cov[e] = v;
+    cov[c2 * nc + c] = v;
+  }
+}
+
 static int64_t outer_nA(const kfac_cov_outer_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
 static int64_t outer_nseg(const kfac_cov_outer_job& j) { return cdiv(j.nG, GSEG); }
 static size_t outer_norm_bytes(const kfac_cov_outer_job& j, int64_t nb) {
@@ -270,6 +381,109 @@ extern "C" int kfac_kron_cov_outer(const kfac_cov_outer_job* jobs, int njobs, in
   hipLaunchKernelGGL(kfac_cov_outer_gram, dim3((unsigned)ng), dim3(NTHREADS), 0, s, args);
   KFAC_CHECK_LAUNCH();
   hipLaunchKernelGGL(kfac_cov_outer_reduce, dim3((unsigned)nb), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}
+
+// ------------------------------------------------------------------ damping sweep
+namespace kfac {
+static int64_t osweep_nA(const kfac_cov_outer_sweep_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
+static int64_t osweep_nseg(const kfac_cov_outer_sweep_job& j) { return cdiv(j.nG, WSEG); }
+static size_t osweep_norm_bytes(const kfac_cov_outer_sweep_job& j, int64_t nb, int nt) {
+  return align_up((size_t)(cdiv(osweep_nA(j), TILE) * nb) * nt * sizeof(float), 256);
+}
+static size_t osweep_v_bytes(const kfac_cov_outer_sweep_job& j, int64_t rows) {
+  return align_up((size_t)rows * (size_t)j.nG * sizeof(float), 256);
+}
+static size_t osweep_partial_bytes(const kfac_cov_outer_sweep_job& j, int64_t nb, int nc, int nt) {
+  return align_up((size_t)(nb * osweep_nseg(j)) * nc * nc * nt * sizeof(float), 256);
+}
+static bool osweep_job_ok(const kfac_cov_outer_sweep_job& q) {
+  return q.a && q.D && q.VA && q.VG && q.wA && q.wG && q.cols > 0 && q.nG > 0 && q.lda >= q.cols &&
+         q.ldD >= q.nG && q.ldA >= osweep_nA(q) && q.ldG >= q.nG && q.ldwA >= osweep_nA(q) &&
+         q.ldwG >= q.nG;
+}
+}  // namespace kfac
+
+extern "C" size_t kfac_kron_cov_outer_sweep_workspace_bytes(const kfac_cov_outer_sweep_job* jobs,
+                                                            int njobs, int64_t nb, int nc, int nt) {
+  if (!jobs || njobs <= 0 || njobs > CMAXJ || nb <= 0 || nc <= 0 || nc > CMAXC || nt <= 0 ||
+      nt > SMAXT)
+    return 0;
+  size_t total = 0;
+  for (int i = 0; i < njobs; ++i) {
+    if (jobs[i].cols <= 0 || jobs[i].nG <= 0) return 0;
+    total += osweep_norm_bytes(jobs[i], nb, nt) + osweep_v_bytes(jobs[i], nb * nc) +
+             osweep_partial_bytes(jobs[i], nb, nc, nt);
+  }
+  return total;
+}
+
+extern "C" int kfac_kron_cov_outer_sweep(const kfac_cov_outer_sweep_job* jobs, int njobs, int64_t nb,
+                                         int nc, int nt, int accumulate, float* cov, void* workspace,
+                                         size_t workspace_bytes, kfac_stream_t stream) {
+  if (!jobs || njobs <= 0 || njobs > CMAXJ || nb <= 0 || nc <= 0 || nc > CMAXC || nt <= 0 ||
+      nt > SMAXT || !cov)
+    return KFAC_EINVAL;
+  for (int i = 0; i < njobs; ++i)
+    if (!osweep_job_ok(jobs[i])) return KFAC_EINVAL;
+  const int64_t lim = (int64_t)1 << 31;
+  // (kfac_kron_cov_outer's limit: 32-bit sample and delta-row columns, 32-bit task counts)
+  if (nb >= (lim - TILE) / nc) return KFAC_EINVAL;
+  const int64_t rows = nb * nc;
+  OuterArgs args{};
+  SweepArgs sw{};
+  args.njobs = njobs;
+  args.nc = nc;
+  args.accumulate = accumulate;
+  args.nb = nb;
+  args.cov = cov;
+  sw.ntau = nt;
+  int64_t nn = 0, nv = 0, ng = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const kfac_cov_outer_sweep_job& q = jobs[i];
+    if (osweep_nA(q) >= lim - TILE) return KFAC_EINVAL;
+    OuterJobDev& d = args.job[i];
+    d.a = q.a; d.D = q.D; d.K1 = q.VA; d.K2 = q.VG;
+    d.lda = q.lda; d.ldD = q.ldD; d.ld1 = q.ldA; d.ld2 = q.ldG;
+    d.cols = q.cols;
+    d.ones = q.has_ones ? q.cols : -1;
+    d.nA = (int)osweep_nA(q);
+    d.nG = q.nG;
+    d.at = (int)cdiv(d.nA, TILE);
+    d.bt = (int)cdiv(nb, TILE);
+    d.tg = (int)cdiv(q.nG, TILE);
+    d.nseg = (int)osweep_nseg(q);
+    d.lower1 = d.lower2 = 0;
+    d.vrows = (int)rows;
+    d.n_begin = (int)nn; d.v_begin = (int)nv; d.g_begin = (int)ng;
+    nn += (int64_t)d.at * d.bt;
+    nv += cdiv(rows, TILE) * d.tg;
+    ng += nb * d.nseg;
+    if (nn >= lim || nv >= lim || ng >= lim) return KFAC_EINVAL;
+    args.n_end[i] = (int)nn; args.v_end[i] = (int)nv; args.g_end[i] = (int)ng;
+    sw.job[i].wA = q.wA; sw.job[i].wG = q.wG;
+    sw.job[i].ldwA = q.ldwA; sw.job[i].ldwG = q.ldwG;
+  }
+  if (!workspace ||
+      workspace_bytes < kfac_kron_cov_outer_sweep_workspace_bytes(jobs, njobs, nb, nc, nt))
+    return KFAC_EWORKSPACE;
+  char* ws = (char*)workspace;
+  for (int i = 0; i < njobs; ++i) {
+    OuterJobDev& d = args.job[i];
+    d.norm = reinterpret_cast<float*>(ws); ws += osweep_norm_bytes(jobs[i], nb, nt);
+    d.V = reinterpret_cast<float*>(ws); ws += osweep_v_bytes(jobs[i], rows);
+    d.partial = reinterpret_cast<float*>(ws); ws += osweep_partial_bytes(jobs[i], nb, nc, nt);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(kfac_cov_rownorm_w, dim3((unsigned)nn), dim3(NTHREADS), 0, s, args, sw);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_outer_v, dim3((unsigned)nv), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_outer_sweep_gram, dim3((unsigned)ng), dim3(NTHREADS), 0, s, args, sw);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_outer_sweep_reduce, dim3((unsigned)nb, (unsigned)nt), dim3(NTHREADS), 0,
+                     s, args);
   KFAC_CHECK_LAUNCH();
   return KFAC_OK;
 }

@@ -28,6 +28,7 @@ from torch import Tensor
 from torch.nn import Module, Sequential
 
 from . import _native as N
+from . import utilities
 
 SUPPORTED = ['Linear', 'Conv2d', 'MultiheadAttention']
 
@@ -69,6 +70,7 @@ class Curvature(ABC):
     def state(self, value):
         self.flush()
         self._state = value
+        self._eig_state = None  # (KFAC.eigh's cache: eigenpairs of the replaced factors)
 
     # `inv_state` reads first settle the verdict of a pending inversion (see
     # KFAC.invert: the device's pivot check is read back asynchronously, so invert()
@@ -309,6 +311,7 @@ class KFAC(Curvature):
         self._fast_alt = []
         self._acc_flush = self._acc_map = None
         self._state = dict()
+        self._eig_state = None
         self.inv_state = dict()
         if self.double_buffer and self._packed is not None:
             self._packed, self._packed_views, self._alt_packed, self._alt_views = (
@@ -466,6 +469,7 @@ class KFAC(Curvature):
     def update(self, batch_size: int):
         """Accumulate this batch's factors for every selected layer
         (curvatures.py:325-365; `batch_size` is unused there too)."""
+        self._eig_state = None
         if self.defer_reduce:
             fast = self._fast
             if fast is not None:
@@ -920,6 +924,27 @@ class KFAC(Curvature):
                                      [t for _, pair in outs for t in pair], side is not None)
         if self.eager_verdict:
             self._check_inverse()
+
+    # ------------------------------------------------------------------ eigh
+    @property
+    def eig_state(self):
+        """The eigenpairs `eigh` cached for the current factors ({} when there are none)."""
+        return self._eig_state or {}
+
+    def eigh(self):
+        """eig_state[layer] = ((lam_A fp64, V_A fp32), (lam_G, V_G)): the eigendecompositions
+        of the symmetrised factors (ascending, eigenvectors as columns), one grouped
+        `utilities.symeig` over `state` (the read completes a deferred reduce).  In this
+        basis a damping is a pair of weight vectors (variance.damping_weights), so a grid
+        of dampings needs one decomposition (variance.glm_predictive_sweep).  Cached until
+        `update`, `reset`, `load` or a `state` assignment; `save` does not write it."""
+        state = self.state
+        assert state, "State dict is empty. Did you call 'update' prior to this?"
+        if self._eig_state is None:
+            layers = list(state)
+            res = utilities.symeig([F_ for layer in layers for F_ in state[layer]], eigenvectors=True)
+            self._eig_state = {layer: (res[2 * i], res[2 * i + 1]) for i, layer in enumerate(layers)}
+        return self._eig_state
 
     def _event(self, device, ordering=True):
         """A raw HIP event (N.RawEvent) from the pool of settled ones (a verdict's `done`

@@ -138,6 +138,7 @@ class DistributedKFAC(KFAC):
     def state(self, value):
         self.flush()
         self._state = value
+        self._eig_state = None
 
     def save(self, filename):
         """Curvature.save of the reduced state; refused while this rank's pass is not
@@ -161,6 +162,7 @@ class DistributedKFAC(KFAC):
         collective over the packed lower triangles of every factor."""
         if not self._pending:
             return
+        self._eig_state = None  # (KFAC.eigh's cache: `state` changes below)
         self.flush()  # the rank-local factors are complete only after the deferred reduce
         # the reduced state may still be in flight on a side stream: a previous pass's
         # side collective unpacks into it and its inversion reads it there; the in-place

@@ -1,8 +1,10 @@
 """Eigen/Kronecker helpers of the KFAC path (models/utilities.py:120-159, 387-409).
 
 `get_eigenvalues` / `get_eigenvectors` keep the reference's signatures and output
-layout; the eigensolves run on the device (libkfac_hip `kfac_syev`, fp64 Jacobi)
-instead of the removed `torch.symeig`.
+layout; the eigensolves run on the device (libkfac_hip `kfac_syev`, fp64: cyclic Jacobi
+in LDS up to n = 128, Householder tridiagonalisation + bisection + inverse iteration
+above) instead of the removed `torch.symeig`.  `symeig(..., eigenvectors=True)` is also
+what `KFAC.eigh` caches for damping sweeps (variance.glm_predictive_sweep).
 """
 from __future__ import annotations
 

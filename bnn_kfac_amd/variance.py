@@ -505,6 +505,272 @@ def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64, ja
     return torch.cat(logits), torch.cat(covs)
 
 
+# ------------------------------------------------------------ damping sweeps
+# A = V_A diag(lam_A) V_A^T (KFAC.eigh) gives KFAC.invert's L_A L_A^T = V_A diag(w_A) V_A^T with
+# w_A = 1 / (sqrt(s) lam_A + sqrt(n)): in the eigenbasis a damping (add n, multiply s) is a
+# pair of weight vectors, and a grid of dampings shares the forward pass, the Jacobians or
+# captures and the projections on V_A / V_G (kfac_kron_cov_sweep, kfac_kron_cov_outer_sweep).
+MAX_SWEEP = 64  # grid points per device call
+
+
+def damping_weights(lam: Tensor, dampings: Sequence[Tuple[float, float]]) -> Tensor:
+    """w[t, i] = 1 / (sqrt(s_t) lam[i] + sqrt(n_t)) for dampings [(add n_t, multiply s_t)]:
+    (nt, n) fp32, computed in fp64 on lam's device.  Raises numpy.linalg.LinAlgError if a
+    shifted eigenvalue is not positive (KFAC.invert's non-SPD condition).  Pure torch."""
+    d = torch.tensor([[float(n), float(s)] for n, s in dampings], dtype=torch.float64,
+                     device=lam.device).reshape(-1, 2)
+    r = d[:, 1:2].sqrt() * lam.detach().to(torch.float64).reshape(1, -1) + d[:, 0:1].sqrt()
+    if not bool((r > 0).all()):
+        raise np.linalg.LinAlgError("damping_weights: sqrt(multiply) * eigenvalue + sqrt(add) is not "
+                                    "positive (the damped factor is not positive definite)")
+    return r.reciprocal().to(torch.float32)
+
+
+def _damping_grid(dampings, count: int):
+    """[[(add, multiply) per state entry] per grid point], each pair parsed as KFAC.invert
+    parses its arguments (scalars, or two per-entry lists)."""
+    from .curvatures import KFAC
+    grid = [KFAC._damping(None, add, multiply, count) for add, multiply in dampings]
+    if not grid:
+        raise ValueError("no dampings")
+    return grid
+
+
+def _sweep_weights(w: Tensor, n: int, what: str):
+    """(w as (nt, n) with unit column stride, its row stride)."""
+    w = w.detach()
+    if w.dim() == 1:
+        w = w.unsqueeze(0)
+    if w.dim() != 2 or w.shape[1] != n:
+        raise ValueError(f"{what} {tuple(w.shape)}: expected (nt, {n})")
+    N.require_device(w, what)
+    if w.stride(1) != 1 or (w.shape[0] > 1 and w.stride(0) < n):
+        w = w.contiguous()
+    return w, (w.stride(0) if w.shape[0] > 1 else n)
+
+
+def _sweep_basis(V: Tensor, what: str):
+    if V.dim() != 2 or V.shape[0] != V.shape[1]:
+        raise ValueError(f"{what} {tuple(V.shape)}: expected a square matrix of eigenvectors")
+    N.require_device(V, what)
+    V = V.detach() if V.stride(-1) == 1 else V.detach().contiguous()
+    return V, max(V.stride(0), V.shape[0])
+
+
+def _run_sweep(build, workspace_bytes, call, njobs, nb, nc, nt, device, max_workspace_bytes):
+    """The chunking the two sweeps share: `build(i, b0, t0)` is job i's struct for samples
+    from b0 and grid points from t0.  Jobs fold in groups of 8, grid points go in calls of
+    MAX_SWEEP, the samples in chunks that need at most `max_workspace_bytes` of scratch."""
+    out = torch.empty(nt, nb, nc, nc, dtype=torch.float32, device=device)
+    if nb == 0:
+        return out
+    groups = [range(i, min(i + 8, njobs)) for i in range(0, njobs, 8)]
+    tmax = min(nt, MAX_SWEEP)
+
+    def need(n):
+        return max(workspace_bytes([build(i, 0, 0) for i in g], n, nc, tmax) for g in groups)
+
+    step = nb
+    while step > 1 and need(step) > max_workspace_bytes:
+        step = max(1, min(step - 1, step * max_workspace_bytes // need(step)))
+    if need(step) > max_workspace_bytes:
+        raise ValueError(f"one sample needs {need(1)} workspace bytes, max_workspace_bytes is "
+                         f"{max_workspace_bytes}")
+    for t0 in range(0, nt, MAX_SWEEP):
+        ntc = min(MAX_SWEEP, nt - t0)
+        for b0 in range(0, nb, step):
+            n = min(step, nb - b0)
+            # a call writes (ntc, n, nc, nc) contiguously: a sample chunk goes through a copy
+            dst = out[t0:t0 + ntc] if n == nb else torch.empty(ntc, n, nc, nc, dtype=torch.float32,
+                                                               device=device)
+            for gi, g in enumerate(groups):
+                call([build(i, b0, t0) for i in g], n, nc, ntc, dst, accumulate=gi > 0)
+            if n != nb:
+                out[t0:t0 + ntc, b0:b0 + n] = dst
+    return out
+
+
+def kron_covariance_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
+                          max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance over a grid of nt weightings in the factors' eigenbasis:
+    cov[t, b, c, c'] = sum_l sum_{i,g} wA_l[t, i] wG_l[t, g] Y_l[b, c][i, g] Y_l[b, c'][i, g],
+    Y_l[b, c] = VA_l^T M_l[b, c] VG_l projected once for all t.
+
+    terms: [(J_l, VA_l, VG_l, wA_l, wG_l)], J as kron_covariance takes it, VA (nA x nA) /
+    VG (nG x nG) eigenvectors as columns, wA (nt, nA) / wG (nt, nG) non-negative weights
+    (damping_weights).  Returns (nt, nb, nc, nc) fp32; per grid point kron_covariance's
+    guarantees hold, and slice t has the bits of the call with row t's weights alone.
+    """
+    if not terms:
+        raise ValueError("no terms")
+    keep, jobs = [], []
+    nb = nc = nt = None
+    for J, VA, VG, wA, wG in terms:
+        VAc, ldA = _sweep_basis(VA, "VA")
+        VGc, ldG = _sweep_basis(VG, "VG")
+        nA, nG = VAc.shape[0], VGc.shape[0]
+        J3, ld = _cov_rows(J, nA * nG)
+        N.require_device(J3, "J")
+        wAc, ldwA = _sweep_weights(wA, nA, "wA")
+        wGc, ldwG = _sweep_weights(wG, nG, "wG")
+        if nb is None:
+            nb, nc, nt = J3.shape[0], J3.shape[1], wAc.shape[0]
+        elif (J3.shape[0], J3.shape[1]) != (nb, nc):
+            raise ValueError("all terms need the same (nb, nc)")
+        if wAc.shape[0] != nt or wGc.shape[0] != nt or nt == 0:
+            raise ValueError("all weights need the same number nt >= 1 of rows")
+        if nc > MAX_COV_CLASSES:
+            raise ValueError(f"kron_covariance_sweep handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        keep.extend([J3, VAc, VGc, wAc, wGc])
+        jobs.append((J3.data_ptr(), ld, nA, nG, VAc.data_ptr(), ldA, VGc.data_ptr(), ldG,
+                     wAc.data_ptr(), ldwA, wGc.data_ptr(), ldwG))
+
+    def build(i, b0, t0):
+        j = jobs[i]
+        return N.CovSweepJob(j[0] + 4 * b0 * nc * j[1], *j[1:8], j[8] + 4 * t0 * j[9], j[9],
+                             j[10] + 4 * t0 * j[11], j[11])
+
+    return _run_sweep(build, N.kron_cov_sweep_workspace_bytes, N.kron_cov_sweep, len(jobs), nb, nc, nt,
+                      keep[0].device, max_workspace_bytes)
+
+
+def kron_covariance_outer_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]],
+                                max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_outer over a grid of nt weightings in the factors' eigenbasis:
+    cov[t, b] = sum_l (sum_i wA_l[t, i] p_l[b][i]^2) Q_l[b] diag(wG_l[t]) Q_l[b]^T with
+    p_l[b] = VA_l^T [a_l[b] | 1] and Q_l[b] = D_l[b] VG_l projected once for all t.
+
+    terms: [(a_l, D_l, VA_l, VG_l, wA_l, wG_l)], a and D as kron_covariance_outer takes them,
+    VA (nA x nA, nA = cols + 1 with the implicit ones column, or cols), VG (nG x nG), wA
+    (nt, nA), wG (nt, nG).  Returns (nt, nb, nc, nc) fp32 with kron_covariance_sweep's
+    guarantees.
+    """
+    if not terms:
+        raise ValueError("no terms")
+    keep, jobs = [], []
+    nb = nc = nt = None
+    for a, D, VA, VG, wA, wG in terms:
+        VAc, ldA = _sweep_basis(VA, "VA")
+        VGc, ldG = _sweep_basis(VG, "VG")
+        nA, nG = VAc.shape[0], VGc.shape[0]
+        D3, ldD = _cov_rows(D, nG)
+        a2 = a.detach()
+        a2 = a2.reshape(1, -1) if a2.dim() == 1 else a2
+        if a2.dim() != 2:
+            raise ValueError(f"a {tuple(a2.shape)}: expected (nb, cols), a Linear layer's 2-D input")
+        cols = a2.shape[1]
+        if nA not in (cols, cols + 1) or cols == 0:
+            raise ValueError(f"a has {cols} columns, VA {tuple(VA.shape)} needs {nA} or {nA - 1}")
+        wAc, ldwA = _sweep_weights(wA, nA, "wA")
+        wGc, ldwG = _sweep_weights(wG, nG, "wG")
+        if nb is None:
+            nb, nc, nt = D3.shape[0], D3.shape[1], wAc.shape[0]
+        elif (D3.shape[0], D3.shape[1]) != (nb, nc):
+            raise ValueError("all terms need the same (nb, nc)")
+        if a2.shape[0] != nb:
+            raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
+        if wAc.shape[0] != nt or wGc.shape[0] != nt or nt == 0:
+            raise ValueError("all weights need the same number nt >= 1 of rows")
+        if nc > MAX_COV_CLASSES:
+            raise ValueError(f"kron_covariance_outer_sweep handles at most {MAX_COV_CLASSES} outputs, "
+                             f"got {nc}")
+        if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols):
+            a2 = a2.contiguous()
+        lda = a2.stride(0) if nb > 1 else cols
+        for t, what in ((a2, "a"), (D3, "D")):
+            N.require_device(t, what)
+        keep.extend([a2, D3, VAc, VGc, wAc, wGc])
+        jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0,
+                     VAc.data_ptr(), ldA, VGc.data_ptr(), ldG, wAc.data_ptr(), ldwA, wGc.data_ptr(), ldwG))
+
+    def build(i, b0, t0):
+        j = jobs[i]
+        return N.CovOuterSweepJob(j[0] + 4 * b0 * j[1], j[1], j[2], j[3], j[4] + 4 * b0 * nc * j[5],
+                                  *j[5:12], j[12] + 4 * t0 * j[13], j[13], j[14] + 4 * t0 * j[15], j[15])
+
+    return _run_sweep(build, N.kron_cov_outer_sweep_workspace_bytes, N.kron_cov_outer_sweep, len(jobs),
+                      nb, nc, nt, keep[0].device, max_workspace_bytes)
+
+
+def glm_predictive_sweep(kfac, x: Tensor, dampings, layers: Iterable = None, chunk: int = 64,
+                         jacobians: str = "dense"):
+    """glm_predictive for a grid of dampings from ONE eigendecomposition of the factors:
+    (logits (N, nc), cov (nt, N, nc, nc)), cov[t] what `kfac.invert(*dampings[t])` followed by
+    glm_predictive gives, without an inversion.  `dampings`: a sequence of (add, multiply),
+    each a scalar pair or two per-layer lists as KFAC.invert takes them.  The forward pass,
+    the Jacobians (or captures) and the projections on the eigenvectors are shared by the
+    grid; each grid point costs one weighted contraction.  Uses `kfac.eig_state`, calling
+    `kfac.eigh()` when nothing is cached.  `jacobians` as in glm_predictive: "factored" sends
+    Linear layers through kron_covariance_outer_sweep and Conv2d layers through
+    kron_covariance_sweep on conv_jacobian_rows."""
+    if jacobians not in ("dense", "factored"):
+        raise ValueError(f"jacobians must be 'dense' or 'factored', got {jacobians!r}")
+    model = kfac.model
+    entries = list(kfac.state)
+    if layers is None:
+        layers = [m for m in list(model.modules())[1:] if m in kfac.state]
+    layers = list(layers)
+    grid = _damping_grid(dampings, len(entries))
+    eig = kfac.eig_state or kfac.eigh()
+    basis = {}
+    for layer in layers:
+        (lamA, VA), (lamG, VG) = eig[layer]
+        pairs = [point[entries.index(layer)] for point in grid]
+        basis[layer] = (VA, VG, damping_weights(lamA, pairs), damping_weights(lamG, pairs))
+    logits, covs = [], []
+    for c0 in range(0, x.shape[0], chunk):
+        xc = x[c0:c0 + chunk]
+        if jacobians == "dense":
+            f, Js = output_jacobians(model, layers, xc)
+            cov = kron_covariance_sweep([(J, *basis[layer]) for layer, J in zip(layers, Js)])
+        else:
+            f, io = layer_io_jacobians(model, layers, xc)
+            outer, dense = [], []
+            for layer, (a, D) in zip(layers, io):
+                if isinstance(layer, torch.nn.Linear):
+                    if a.dim() != 2:
+                        raise ValueError(f"the factored route needs 2-D Linear inputs, got {tuple(a.shape)}")
+                    outer.append((a, D, *basis[layer]))
+                elif isinstance(layer, torch.nn.Conv2d):
+                    dense.append((conv_jacobian_rows(layer, a, D), *basis[layer]))
+                else:
+                    raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
+                                     f"{layer.__class__.__name__}")
+            cov = kron_covariance_outer_sweep(outer) if outer else None
+            if dense:
+                conv = kron_covariance_sweep(dense)
+                cov = conv if cov is None else cov + conv
+        logits.append(f)
+        covs.append(cov)
+    return torch.cat(logits), torch.cat(covs, dim=1)
+
+
+def log_det_sweep(eig_state, dampings) -> Tensor:
+    """log det of the damped Kronecker curvature per grid point, from the eigenvalues:
+    out[t] = sum_layers nG sum_i log(sqrt(s) lamA[i] + sqrt(n)) + nA sum_g log(sqrt(s) lamG[g] + sqrt(n))
+           = -2 sum_layers (nG sum log diag L_A + nA sum log diag L_G)   of KFAC.invert's factors,
+    the other half of an evidence-style criterion.  `eig_state`: KFAC.eigh's dictionary, or
+    the KFAC object (its cached eigenpairs, else eigh()).  Returns (nt,) fp64.  Pure torch."""
+    if not isinstance(eig_state, dict):
+        eig_state = eig_state.eig_state or eig_state.eigh()
+    entries = list(eig_state.values())
+    grid = _damping_grid(dampings, len(entries))
+    lam0 = entries[0][0][0]
+    out = torch.zeros(len(grid), dtype=torch.float64, device=lam0.device)
+    for index, ((lamA, _), (lamG, _)) in enumerate(entries):
+        d = torch.tensor([[float(point[index][0]), float(point[index][1])] for point in grid],
+                         dtype=torch.float64, device=lam0.device)
+        terms = []
+        for lam in (lamA, lamG):
+            r = d[:, 1:2].sqrt() * lam.detach().to(torch.float64).reshape(1, -1) + d[:, 0:1].sqrt()
+            if not bool((r > 0).all()):
+                raise np.linalg.LinAlgError("log_det_sweep: sqrt(multiply) * eigenvalue + sqrt(add) is "
+                                            "not positive (the damped factor is not positive definite)")
+            terms.append(r.log().sum(dim=1))
+        out += lamG.numel() * terms[0] + lamA.numel() * terms[1]
+    return out
+
+
 def probit_predictive(logits: Tensor, cov: Tensor) -> Tensor:
     """softmax(logits / sqrt(1 + pi/8 * diag(cov))): the probit approximation of
     E[softmax(f)] for f ~ N(logits, cov).  Pure torch."""

@@ -296,6 +296,63 @@ KFAC_API int kfac_kron_cov_outer(const kfac_cov_outer_job* jobs, int njobs, int6
                                  int accumulate, float* cov, void* workspace, size_t workspace_bytes,
                                  kfac_stream_t stream);
 
+/* ------------------------------ GLM predictive covariance over a damping grid
+ * With A = VA diag(lamA) VA^T and G = VG diag(lamG) VG^T (kfac_syev), kfac_invert's
+ * factors satisfy L_A L_A^T = VA diag(wA) VA^T, wA[i] = 1 / (sqrt(s) lamA[i] + sqrt(n)),
+ * and likewise for G: in the eigenbasis a damping (n, s) is a pair of weight vectors.
+ * For nt of them at once (1 <= nt <= 64), cov is nt x nb x nc x nc:
+ *   kfac_kron_cov_sweep        Y_{b,c} = VA^T M_{b,c} VG once per call, then
+ *     cov[t][b][c][c'] (+)= sum_j sum_{i,g} wA_t[i] wG_t[g] Y_{b,c}[i][g] Y_{b,c'}[i][g]
+ *   kfac_kron_cov_outer_sweep  p_b = VA^T abar_b and Q_b = Delta_b VG once per call, then
+ *     cov[t][b] (+)= sum_j (sum_i wA_t[i] p_b[i]^2) * Q_b diag(wG_t) Q_b^T
+ * The weights are plain non-negative numbers (the calls know nothing of damping); row t
+ * of wA / wG is grid point t.  The guarantees of kfac_kron_cov / kfac_kron_cov_outer hold
+ * per grid point (fixed-order fp64 reduction, no atomics, bitwise symmetric blocks, a
+ * sample's block depends on that sample only), and slice t of an nt-call has the bits of
+ * the nt = 1 call with row t's weights.  At most 8 jobs and nc <= 32 per call.         */
+typedef struct kfac_cov_sweep_job {
+  const float* J; /* as kfac_cov_job */
+  int64_t ldJ;
+  int32_t nA, nG;
+  const float* VA; /* nA x nA, eigenvectors as columns (kfac_syev's evecs) */
+  int64_t ldA;
+  const float* VG; /* nG x nG */
+  int64_t ldG;
+  const float* wA; /* nt x nA, row t at wA + t*ldwA */
+  int64_t ldwA;
+  const float* wG; /* nt x nG */
+  int64_t ldwG;
+} kfac_cov_sweep_job;
+
+KFAC_API size_t kfac_kron_cov_sweep_workspace_bytes(const kfac_cov_sweep_job* jobs, int njobs,
+                                                    int64_t nb, int nc, int nt);
+KFAC_API int kfac_kron_cov_sweep(const kfac_cov_sweep_job* jobs, int njobs, int64_t nb, int nc, int nt,
+                                 int accumulate, float* cov, void* workspace, size_t workspace_bytes,
+                                 kfac_stream_t stream);
+
+typedef struct kfac_cov_outer_sweep_job {
+  const float* a; /* as kfac_cov_outer_job */
+  int64_t lda;
+  int32_t cols, has_ones;
+  const float* D;
+  int64_t ldD;
+  int32_t nG, reserved;
+  const float* VA; /* nA x nA, nA = cols + has_ones */
+  int64_t ldA;
+  const float* VG; /* nG x nG */
+  int64_t ldG;
+  const float* wA; /* nt x nA */
+  int64_t ldwA;
+  const float* wG; /* nt x nG */
+  int64_t ldwG;
+} kfac_cov_outer_sweep_job;
+
+KFAC_API size_t kfac_kron_cov_outer_sweep_workspace_bytes(const kfac_cov_outer_sweep_job* jobs,
+                                                          int njobs, int64_t nb, int nc, int nt);
+KFAC_API int kfac_kron_cov_outer_sweep(const kfac_cov_outer_sweep_job* jobs, int njobs, int64_t nb,
+                                       int nc, int nt, int accumulate, float* cov, void* workspace,
+                                       size_t workspace_bytes, kfac_stream_t stream);
+
 /* -------------------------------------------------------- posterior samples
  * out_j = (LA_j Z_j LG_j^T)^T, shape (nG x nA): KFAC.sample, curvatures.py:400-405,
  * with Z (nA x nG row-major) supplied by the caller (torch.randn, the reference's

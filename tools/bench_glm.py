@@ -20,6 +20,18 @@ by call in one session:
                   their dense rows against kron_covariance_outer on (input, output Jacobian)
   glm_dense_ms / glm_factored_ms : glm_predictive end to end, both ways
   factored_max_diff_over_max : the two end-to-end covariances, max |diff| / max
+`--sweep NT` instead times the damping grid (glm_predictive_sweep) on mlp (factored),
+basenet15k (dense) and c5 (factored; `--workloads` selects, one JSON line per workload as it
+finishes -- C5's eigh() alone takes minutes), for the grid sizes 1, 4, 16 and NT:
+  eigh_ms                 : the one-off KFAC.eigh() (cache dropped before every call)
+  sweep_ms[nt]            : glm_predictive_sweep over nt dampings, eigenpairs cached
+  loop_ms[nt]             : the same grid as a loop of kfac.invert + glm_predictive
+  sweep_cov_ms / loop_cov_ms[nt] : the covariance calls alone on fixed Jacobians or
+                            captures (the sweep kernel once; the plain kernel nt times)
+  marginal_ms_per_damping : (sweep_ms[16] - sweep_ms[1]) / 15, against
+  loop_ms_per_damping     : loop_ms[16] / 16
+  sweep_max_diff_over_max : the sweep against the loop's covariances, max |diff| / max
+all alternated call by call in one session.
 GPU times are HIP-event times of single calls after a warm-up, medians over `--reps`
 calls.  apply_flops / gram_bytes are the algorithmic work (2 nA^2 nG + 2 nA nG^2 per
 row, halved for the skipped triangle; T read once) for a roofline over kernel times
@@ -38,8 +50,9 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bnn_kfac_amd import _native as N  # noqa: E402
 from bnn_kfac_amd.curvatures import KFAC  # noqa: E402
-from bnn_kfac_amd.variance import (glm_predictive, kron_covariance, kron_covariance_outer,  # noqa: E402
-                                   layer_io_jacobians, output_jacobians)
+from bnn_kfac_amd.variance import (damping_weights, glm_predictive, glm_predictive_sweep,  # noqa: E402
+                                   kron_covariance, kron_covariance_outer, kron_covariance_outer_sweep,
+                                   kron_covariance_sweep, layer_io_jacobians, output_jacobians)
 
 
 def mlp():
@@ -175,8 +188,72 @@ def run(name, make, dev, args):
     return res
 
 
+def damping_grid(nt):
+    """nt dampings (add, multiply): add log-spaced over 1e-4 .. 1 at multiply 200."""
+    return [(10.0 ** (-4.0 + 4.0 * i / max(1, nt - 1)), 200.0) for i in range(nt)]
+
+
+def run_sweep(make, route, dev, args):
+    net, kfac, layers, x, nb = fit(make, dev)
+    res = {"nb": nb, "route": route, "layers": [[A.shape[0], G.shape[0]] for A, G in kfac.state.values()]}
+
+    def eigh():
+        kfac._eig_state = None
+        kfac.eigh()
+
+    res["eigh_ms"] = event_ms(eigh, 1, 3)
+    eig = kfac.eigh()
+    if route == "factored":
+        _, io = layer_io_jacobians(net, layers, x)
+        fixed = [(a, D) for a, D in io]
+        plain, sweep = kron_covariance_outer, kron_covariance_outer_sweep
+    else:
+        fixed = [(J.contiguous(),) for J in output_jacobians(net, layers, x)[1]]
+        plain, sweep = kron_covariance, kron_covariance_sweep
+    sizes = sorted({1, 4, 16, args.sweep})
+    for key in ("sweep_ms", "loop_ms", "sweep_cov_ms", "loop_cov_ms"):
+        res[key] = {}
+    for nt in sizes:
+        grid = damping_grid(nt)
+
+        def loop():
+            out = []
+            for add, multiply in grid:
+                kfac.invert(add, multiply)
+                out.append(glm_predictive(kfac, x, chunk=nb, jacobians=route)[1])
+            return out
+
+        sweep_terms = [(*f, eig[l][0][1], eig[l][1][1], damping_weights(eig[l][0][0], grid),
+                        damping_weights(eig[l][1][0], grid)) for l, f in zip(layers, fixed)]
+        kfac.invert(*grid[0])
+        loop_terms = [(*f, *kfac.inv_state[l]) for l, f in zip(layers, fixed)]
+
+        def loop_cov():
+            for _ in grid:
+                plain(loop_terms)
+
+        reps = max(3, args.reps // (1 + nt // 4))
+        res["sweep_ms"][nt], res["loop_ms"][nt], res["sweep_cov_ms"][nt], res["loop_cov_ms"][nt] = alternate_ms(
+            [lambda: glm_predictive_sweep(kfac, x, grid, chunk=nb, jacobians=route), loop,
+             lambda: sweep(sweep_terms), loop_cov], args.warmup if nt <= 4 else 2, reps)
+        if nt == sizes[-1]:
+            got = glm_predictive_sweep(kfac, x, grid, chunk=nb, jacobians=route)[1]
+            want = torch.stack(loop())
+            res["sweep_max_diff_over_max"] = float(((got - want).abs().amax(dim=(1, 2, 3)) /
+                                                    want.abs().amax(dim=(1, 2, 3))).max())
+    res["marginal_ms_per_damping"] = (res["sweep_ms"][16] - res["sweep_ms"][1]) / 15
+    res["loop_ms_per_damping"] = res["loop_ms"][16] / 16
+    res["marginal_cov_ms_per_damping"] = (res["sweep_cov_ms"][16] - res["sweep_cov_ms"][1]) / 15
+    res["loop_cov_ms_per_damping"] = res["loop_cov_ms"][16] / 16
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="mlp,basenet15k,c5",
+                    help="--sweep: which of mlp, basenet15k, c5 to run (one JSON line each, then the whole)")
+    ap.add_argument("--sweep", type=int, default=0, metavar="NT",
+                    help="time the damping grid (glm_predictive_sweep) at 1, 4, 16 and NT dampings instead")
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", choices=["all", "cov"], default="all",
@@ -184,6 +261,15 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     out = {"workload": "GLM predictive covariance", "lib": N.LIB_PATH}
+    if args.sweep:
+        out["workload"] = "GLM predictive over a damping grid"
+        for name, make, route in (("mlp", mlp, "factored"), ("basenet15k", basenet15k, "dense"),
+                                  ("c5", c5, "factored")):
+            if name in args.workloads.split(","):
+                out[name] = run_sweep(make, route, dev, args)
+                print(json.dumps({name: out[name]}), flush=True)
+        print(json.dumps(out))
+        return
     for name, make in (("mlp", mlp), ("basenet15k", basenet15k)):
         out[name] = run(name, make, dev, args)
     if args.only == "all":
