@@ -152,6 +152,15 @@ SIGNATURES = {
                                                               c_i64, ctypes.c_int]),
     "kfac_kron_cov_outer": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
                                            ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_kron_cov_joint_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64,
+                                                              ctypes.c_int]),
+    "kfac_kron_cov_joint": (ctypes.c_int, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                           ctypes.c_int, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_kron_cov_outer_joint_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovOuterJob),
+                                                                    ctypes.c_int, c_i64, ctypes.c_int]),
+    "kfac_kron_cov_outer_joint": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64,
+                                                 ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_vp,
+                                                 ctypes.c_size_t, c_vp]),
     "kfac_kron_cov_sweep_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovSweepJob), ctypes.c_int,
                                                               c_i64, ctypes.c_int, ctypes.c_int]),
     "kfac_kron_cov_sweep": (ctypes.c_int, [ctypes.POINTER(CovSweepJob), ctypes.c_int, c_i64, ctypes.c_int,
@@ -501,6 +510,49 @@ def kron_cov_outer(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool =
     ws = workspace.get(out.device, need)
     check(L.kfac_kron_cov_outer(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
                                 stream_handle(out.device)), "kfac_kron_cov_outer")
+
+
+def kron_cov_joint_workspace_bytes(jobs, nb: int, nc: int) -> int:
+    return lib().kfac_kron_cov_joint_workspace_bytes(as_array(CovJob, jobs), len(jobs), nb, nc)
+
+
+def _joint_out(out: torch.Tensor, nb: int, nc: int, what: str):
+    """The joint calls write nb*nc rows of nb*nc floats, out.stride(0) apart: refuse a view
+    they would write outside of."""
+    R = nb * nc
+    if out.dim() != 2 or out.shape[0] < R or out.shape[1] < R or out.stride(1) != 1 or out.stride(0) < R:
+        raise ValueError(f"{what}: out must be 2-D, at least ({R}, {R}), with unit column stride, got "
+                         f"{tuple(out.shape)} / {out.stride()}")
+    require_device(out, what)
+
+
+def kron_cov_joint(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_kron_cov_joint: out (nb*nc, >= nb*nc) with unit column stride (+)= sum_j T_j T_j^T
+    over ALL rows of the call, <= 8 jobs per call."""
+    _joint_out(out, nb, nc, "kron_cov_joint")
+    L = lib()
+    arr = as_array(CovJob, jobs)
+    need = L.kfac_kron_cov_joint_workspace_bytes(arr, len(jobs), nb, nc)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_kron_cov_joint(arr, len(jobs), nb, nc, int(accumulate), ptr(out), out.stride(0), ptr(ws),
+                                ws.numel(), stream_handle(out.device)), "kfac_kron_cov_joint")
+
+
+def kron_cov_outer_joint_workspace_bytes(jobs, nb: int, nc: int) -> int:
+    return lib().kfac_kron_cov_outer_joint_workspace_bytes(as_array(CovOuterJob, jobs), len(jobs), nb, nc)
+
+
+def kron_cov_outer_joint(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_kron_cov_outer_joint: out (nb*nc, >= nb*nc) (+)= sum_j S_j[b, b'] W_j[r, r'], <= 8 jobs
+    per call."""
+    _joint_out(out, nb, nc, "kron_cov_outer_joint")
+    L = lib()
+    arr = as_array(CovOuterJob, jobs)
+    need = L.kfac_kron_cov_outer_joint_workspace_bytes(arr, len(jobs), nb, nc)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_kron_cov_outer_joint(arr, len(jobs), nb, nc, int(accumulate), ptr(out), out.stride(0),
+                                      ptr(ws), ws.numel(), stream_handle(out.device)),
+          "kfac_kron_cov_outer_joint")
 
 
 def kron_cov_sweep_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:

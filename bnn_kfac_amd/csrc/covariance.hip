@@ -31,29 +31,6 @@ namespace kfac {
 
 constexpr int KFAC_ROWBATCH = 16;   // panel layout of [M_0 | M_1 | ...] (internal to this file)
 
-struct CovJobDev {
-  const float* J;
-  const float* K1;
-  const float* K2;
-  float* U;        // rows x nA*nG
-  float* T;        // rows x nA*nG, row r = K1^T M_r K2 in a*nG + g order
-  float* partial;  // nb x nseg x nc*nc
-  int64_t ldJ, ld1, ld2;
-  int nA, nG, tg, nseg, lower1, lower2;
-  int ucols, trows;                // rows*nG, rows*nA
-  int u_begin, t_begin, g_begin;   // first task in the U / T / gram launch
-};
-
-struct CovArgs {
-  int njobs, nc, accumulate;
-  int nu, nt, ng;  // tasks of the U / T / gram launch
-  int64_t nb;
-  float* cov;
-  int u_end[CMAXJ], t_end[CMAXJ], g_end[CMAXJ];
-  CovJobDev job[CMAXJ];
-};
-static_assert(sizeof(CovArgs) <= 4096, "kernel argument block");
-
 // element (k, j) = p[(j / L) * sB + k * L + j % L]: row j / L of J viewed (nA x nG), L = nG
 __device__ __forceinline__ OpDev rowbatch_op(const float* p, int rows, int cols, int64_t L, int64_t sB) {
   OpDev d{};
@@ -231,18 +208,19 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_sweep_reduce(CovArgs args) 
   }
 }
 
-static size_t cov_t_bytes(const kfac_cov_job& j, int64_t rows) {
-  return align_up((size_t)rows * (size_t)j.nA * (size_t)j.nG * sizeof(float), 256);
+// The two apply launches alone (kfac_kron_cov_joint forms its own Gram from T).
+int cov_launch_apply(const CovArgs& args, hipStream_t s) {
+  hipLaunchKernelGGL(kfac_cov_apply_u, dim3((unsigned)args.nu), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(kfac_cov_apply_t, dim3((unsigned)args.nt), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
 }
+
 static int64_t cov_nseg(const kfac_cov_job& j) { return cdiv((int64_t)j.nA * j.nG, GSEG); }
 static size_t cov_partial_bytes(const kfac_cov_job& j, int64_t nb, int nc) {
   return align_up((size_t)(nb * cov_nseg(j)) * nc * nc * sizeof(float), 256);
 }
-static bool cov_job_ok(const kfac_cov_job& q) {
-  return q.J && q.K1 && q.K2 && q.nA > 0 && q.nG > 0 && q.ld1 >= q.nA && q.ld2 >= q.nG &&
-         q.ldJ >= (int64_t)q.nA * q.nG;
-}
-
 }  // namespace kfac
 
 using namespace kfac;
@@ -274,28 +252,16 @@ extern "C" int kfac_kron_cov(const kfac_cov_job* jobs, int njobs, int64_t nb, in
   args.accumulate = accumulate;
   args.nb = nb;
   args.cov = cov;
-  int64_t nu = 0, nt = 0, ng = 0;
+  if (!cov_fill_apply(jobs, njobs, rows, args)) return KFAC_EINVAL;
+  const int64_t nu = args.nu, nt = args.nt;
+  int64_t ng = 0;
   for (int i = 0; i < njobs; ++i) {
-    const kfac_cov_job& q = jobs[i];
-    // the stacked operands are indexed with 32-bit columns: rows*nG and rows*nA (and
-    // with them every launch's task count) stay below 2^31
-    if (rows * q.nG >= lim - TILE || rows * q.nA >= lim - TILE) return KFAC_EINVAL;
     CovJobDev& d = args.job[i];
-    d.J = q.J; d.K1 = q.K1; d.K2 = q.K2;
-    d.ldJ = q.ldJ; d.ld1 = q.ld1; d.ld2 = q.ld2;
-    d.nA = q.nA; d.nG = q.nG;
-    d.tg = (int)cdiv(q.nG, TILE);
-    d.nseg = (int)cov_nseg(q);
-    d.lower1 = q.lower1 != 0;
-    d.lower2 = q.lower2 != 0;
-    d.ucols = (int)(rows * q.nG);
-    d.trows = (int)(rows * q.nA);
-    d.u_begin = (int)nu; d.t_begin = (int)nt; d.g_begin = (int)ng;
-    nu += cdiv(q.nA, TILE) * cdiv(d.ucols, TILE);
-    nt += cdiv(d.trows, TILE) * d.tg;
+    d.nseg = (int)cov_nseg(jobs[i]);
+    d.g_begin = (int)ng;
     ng += nb * d.nseg;
-    if (nu >= lim || nt >= lim || ng >= lim) return KFAC_EINVAL;
-    args.u_end[i] = (int)nu; args.t_end[i] = (int)nt; args.g_end[i] = (int)ng;
+    if (ng >= lim) return KFAC_EINVAL;
+    args.g_end[i] = (int)ng;
   }
   if (!workspace || workspace_bytes < kfac_kron_cov_workspace_bytes(jobs, njobs, nb, nc))
     return KFAC_EWORKSPACE;

@@ -2,7 +2,9 @@
 // share: the limits of one call, the operand views, and the bodies of the two kernels
 // both routes run -- a 64x64 tile of (tall matrix) x K2, and one K segment of a sample's
 // nc x nc Gram block -- and what their damping sweeps share: the weight views and the
-// weighted Gram of a staged segment for a group of grid points.
+// weighted Gram of a staged segment for a group of grid points; and what the joint calls
+// (covariance_joint.hip) take from both: the argument blocks of the apply / V launches, the
+// Abar^T panel, and the 64x64 Gram tile all three of their operands go through.
 #pragma once
 
 #include "kfac_common.h"
@@ -176,6 +178,203 @@ __device__ __forceinline__ void cov_wgram_segment(const float* Tb, int64_t K, in
       }
     }
   }
+}
+
+// ---- what the joint calls (covariance_joint.hip) share with the per-sample ones: the
+// argument blocks of the apply / V launches, the Abar^T panel, the job checks
+struct CovJobDev {
+  const float* J;
+  const float* K1;
+  const float* K2;
+  float* U;        // rows x nA*nG
+  float* T;        // rows x nA*nG, row r = K1^T M_r K2 in a*nG + g order
+  float* partial;  // nb x nseg x nc*nc
+  int64_t ldJ, ld1, ld2;
+  int nA, nG, tg, nseg, lower1, lower2;
+  int ucols, trows;                // rows*nG, rows*nA
+  int u_begin, t_begin, g_begin;   // first task in the U / T / gram launch
+};
+
+struct CovArgs {
+  int njobs, nc, accumulate;
+  int nu, nt, ng;  // tasks of the U / T / gram launch
+  int64_t nb;
+  float* cov;
+  int u_end[CMAXJ], t_end[CMAXJ], g_end[CMAXJ];
+  CovJobDev job[CMAXJ];
+};
+static_assert(sizeof(CovArgs) <= 4096, "kernel argument block");
+
+struct OuterJobDev {
+  const float* a;
+  const float* D;
+  const float* K1;
+  const float* K2;
+  float* norm;     // at x nb: sum over column tile t of (abar_b K1)^2
+  float* V;        // nb*nc x nG
+  float* partial;  // nb x nseg x nc*nc
+  int64_t lda, ldD, ld1, ld2;
+  int cols, ones, nA, nG;  // ones = cols if has_ones else -1
+  int at, bt, tg, nseg, lower1, lower2;
+  int vrows;                       // nb*nc
+  int n_begin, v_begin, g_begin;   // first task in the rownorm / V / gram launch
+};
+
+struct OuterArgs {
+  int njobs, nc, accumulate;
+  int64_t nb;
+  float* cov;
+  int n_end[CMAXJ], v_end[CMAXJ], g_end[CMAXJ];
+  OuterJobDev job[CMAXJ];
+};
+static_assert(sizeof(OuterArgs) <= 4096, "kernel argument block");
+
+// kfac_cov_apply_u + kfac_cov_apply_t (covariance.hip) on a filled block: U, then T, for
+// all rows of every job; kfac_cov_outer_v (covariance_outer.hip): V = Delta K2.
+int cov_launch_apply(const CovArgs& args, hipStream_t s);
+int cov_launch_outer_v(const OuterArgs& args, int64_t nv, hipStream_t s);
+
+constexpr int KFAC_SAMPLEROWS = 17;  // panel layout of Abar^T (internal to the outer routes)
+
+// element (k, b) = k < rows ? p[b * ld + k] : (k == ones ? 1 : 0): Abar^T, samples as
+// the operand's columns.  rows = the stored columns of a, cols = nb.
+__device__ __forceinline__ OpDev samplerows_op(const float* p, int kcols, int ones, int nb,
+                                               int64_t ld) {
+  OpDev d{};
+  d.ptr = p; d.layout = KFAC_SAMPLEROWS; d.rows = kcols; d.cols = nb; d.ld = ld; d.ones = ones;
+  return d;
+}
+
+// Panel<CHANNEL>'s thread map (32 lanes walk k, contiguous in a sample's row) with the
+// ones entry on the K axis: row k == ones of the panel is 1 for every sample.
+template <>
+struct Panel<KFAC_SAMPLEROWS> {
+  static constexpr int PITCH = LDP;
+  const float* base;
+  int64_t ld, kend;
+  int r, c0, col0, nb, krows, ones;
+  __device__ __forceinline__ void init(const OpDev& op, const float* base_, int col0_, int tid,
+                                       int64_t k_end, int64_t) {
+    base = base_; ld = op.ld; kend = k_end; nb = op.cols; krows = (int)op.rows; ones = op.ones;
+    r = tid & 31; c0 = tid >> 5; col0 = col0_;
+  }
+  __device__ __forceinline__ void load(int64_t k, float (&v)[8]) const {
+    const int64_t kk = k + r;
+    const bool ok = kk < kend;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const int b = col0 + c0 + 8 * m;
+      float x = 0.f;
+      if (ok && b < nb) x = kk < krows ? base[(int64_t)b * ld + kk] : (kk == ones ? 1.f : 0.f);
+      v[m] = x;
+    }
+  }
+  __device__ __forceinline__ void store(float* lds, const float (&v)[8]) const {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) lds[r * LDP + c0 + 8 * m] = v[m];
+  }
+};
+
+static inline size_t cov_t_bytes(const kfac_cov_job& j, int64_t rows) {
+  return align_up((size_t)rows * (size_t)j.nA * (size_t)j.nG * sizeof(float), 256);
+}
+static inline bool cov_job_ok(const kfac_cov_job& q) {
+  return q.J && q.K1 && q.K2 && q.nA > 0 && q.nG > 0 && q.ld1 >= q.nA && q.ld2 >= q.nG &&
+         q.ldJ >= (int64_t)q.nA * q.nG;
+}
+static inline int64_t outer_nA(const kfac_cov_outer_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
+static inline size_t outer_v_bytes(const kfac_cov_outer_job& j, int64_t rows) {
+  return align_up((size_t)rows * (size_t)j.nG * sizeof(float), 256);
+}
+static inline bool outer_job_ok(const kfac_cov_outer_job& q) {
+  return q.a && q.D && q.K1 && q.K2 && q.cols > 0 && q.nG > 0 && q.lda >= q.cols &&
+         q.ldD >= q.nG && q.ld1 >= outer_nA(q) && q.ld2 >= q.nG;
+}
+
+// The apply part of a CovArgs block (jobs' operands, the U / T task ranges, nu, nt) for
+// `rows` rows per job; U, T and the Gram fields are the caller's.  The stacked operands
+// are indexed with 32-bit columns: false where rows*nG, rows*nA or a task count reach 2^31.
+static inline bool cov_fill_apply(const kfac_cov_job* jobs, int njobs, int64_t rows, CovArgs& args) {
+  const int64_t lim = (int64_t)1 << 31;
+  int64_t nu = 0, nt = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const kfac_cov_job& q = jobs[i];
+    if (rows * q.nG >= lim - TILE || rows * q.nA >= lim - TILE) return false;
+    CovJobDev& d = args.job[i];
+    d.J = q.J; d.K1 = q.K1; d.K2 = q.K2;
+    d.ldJ = q.ldJ; d.ld1 = q.ld1; d.ld2 = q.ld2;
+    d.nA = q.nA; d.nG = q.nG;
+    d.tg = (int)cdiv(q.nG, TILE);
+    d.lower1 = q.lower1 != 0;
+    d.lower2 = q.lower2 != 0;
+    d.ucols = (int)(rows * q.nG);
+    d.trows = (int)(rows * q.nA);
+    d.u_begin = (int)nu; d.t_begin = (int)nt;
+    nu += cdiv(q.nA, TILE) * cdiv(d.ucols, TILE);
+    nt += cdiv(d.trows, TILE) * d.tg;
+    if (nu >= lim || nt >= lim) return false;
+    args.u_end[i] = (int)nu; args.t_end[i] = (int)nt;
+  }
+  args.nu = (int)nu; args.nt = (int)nt;
+  return true;
+}
+
+// The projection part of an OuterArgs block (jobs' operands, the Abar K1 and Delta K2 task
+// ranges; nn, nv their task counts) for nb samples and `rows` = nb*nc delta rows; norm, V
+// and the Gram fields are the caller's.  false where nA or a task count reach 2^31.
+static inline bool cov_fill_outer(const kfac_cov_outer_job* jobs, int njobs, int64_t nb, int64_t rows,
+                                  OuterArgs& args, int64_t& nn, int64_t& nv) {
+  const int64_t lim = (int64_t)1 << 31;
+  nn = nv = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const kfac_cov_outer_job& q = jobs[i];
+    if (outer_nA(q) >= lim - TILE) return false;
+    OuterJobDev& d = args.job[i];
+    d.a = q.a; d.D = q.D; d.K1 = q.K1; d.K2 = q.K2;
+    d.lda = q.lda; d.ldD = q.ldD; d.ld1 = q.ld1; d.ld2 = q.ld2;
+    d.cols = q.cols;
+    d.ones = q.has_ones ? q.cols : -1;
+    d.nA = (int)outer_nA(q);
+    d.nG = q.nG;
+    d.at = (int)cdiv(d.nA, TILE);
+    d.bt = (int)cdiv(nb, TILE);
+    d.tg = (int)cdiv(q.nG, TILE);
+    d.lower1 = q.lower1 != 0;
+    d.lower2 = q.lower2 != 0;
+    d.vrows = (int)rows;
+    d.n_begin = (int)nn; d.v_begin = (int)nv;
+    nn += (int64_t)d.at * d.bt;
+    nv += cdiv(rows, TILE) * d.tg;
+    if (nn >= lim || nv >= lim) return false;
+    args.n_end[i] = (int)nn; args.v_end[i] = (int)nv;
+  }
+  return true;
+}
+
+// ---- joint covariance (kfac_kron_cov_joint / kfac_kron_cov_outer_joint)
+constexpr int JSEG = GSEG;          // K elements per joint-gram task: a function of K alone
+constexpr int JTILE2 = TILE * TILE; // floats per tile partial
+
+// One 64x64 tile (ti >= tj) of X X^T over the K segment [k0, k1): X is rows x K with K
+// contiguous per row, part the fp32 64x64 partial (row-major, row = the tile-ti row).  The
+// four waves hold one 32x32 quadrant each (contract_tile's normal mode), so element
+// (r, r') is one k-ordered fma chain over the segment from 0: it depends on rows r and r'
+// and on [k0, k1) only, not on the tile it sits in.  A diagonal tile stages one panel
+// (`same`) and skips its upper quadrant, which is never read.
+__device__ __forceinline__ void cov_joint_gram_tile(const float* X, int64_t K, int rows, int ti, int tj,
+                                                    int64_t k0, int64_t k1, float* part, float* lds) {
+  const OpDev x = channel_op(X, K, rows, K);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool same = ti == tj;
+  const bool active = !(same && wave == 1);  // quadrant (0, 1) of a diagonal tile
+  floatx16 acc;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+  contract_tile<KFAC_CHANNEL, KFAC_CHANNEL>(x, ti * TILE, x, tj * TILE, k0, k1, same, active, lds, acc);
+  if (!active) return;
+  float* dst = part + (wave >> 1) * 32 * TILE + (wave & 1) * 32 + (lane & 31);
+#pragma unroll
+  for (int v = 0; v < 16; ++v) dst[acc_row(v, lane) * TILE] = acc[v];
 }
 
 }  // namespace kfac

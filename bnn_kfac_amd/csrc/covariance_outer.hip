@@ -30,71 +30,6 @@
 
 namespace kfac {
 
-constexpr int KFAC_SAMPLEROWS = 17;  // panel layout of Abar^T (internal to this file)
-
-struct OuterJobDev {
-  const float* a;
-  const float* D;
-  const float* K1;
-  const float* K2;
-  float* norm;     // at x nb: sum over column tile t of (abar_b K1)^2
-  float* V;        // nb*nc x nG
-  float* partial;  // nb x nseg x nc*nc
-  int64_t lda, ldD, ld1, ld2;
-  int cols, ones, nA, nG;  // ones = cols if has_ones else -1
-  int at, bt, tg, nseg, lower1, lower2;
-  int vrows;                       // nb*nc
-  int n_begin, v_begin, g_begin;   // first task in the rownorm / V / gram launch
-};
-
-struct OuterArgs {
-  int njobs, nc, accumulate;
-  int64_t nb;
-  float* cov;
-  int n_end[CMAXJ], v_end[CMAXJ], g_end[CMAXJ];
-  OuterJobDev job[CMAXJ];
-};
-static_assert(sizeof(OuterArgs) <= 4096, "kernel argument block");
-
-// element (k, b) = k < rows ? p[b * ld + k] : (k == ones ? 1 : 0): Abar^T, samples as
-// the operand's columns.  rows = the stored columns of a, cols = nb.
-__device__ __forceinline__ OpDev samplerows_op(const float* p, int kcols, int ones, int nb,
-                                               int64_t ld) {
-  OpDev d{};
-  d.ptr = p; d.layout = KFAC_SAMPLEROWS; d.rows = kcols; d.cols = nb; d.ld = ld; d.ones = ones;
-  return d;
-}
-
-// Panel<CHANNEL>'s thread map (32 lanes walk k, contiguous in a sample's row) with the
-// ones entry on the K axis: row k == ones of the panel is 1 for every sample.
-template <>
-struct Panel<KFAC_SAMPLEROWS> {
-  static constexpr int PITCH = LDP;
-  const float* base;
-  int64_t ld, kend;
-  int r, c0, col0, nb, krows, ones;
-  __device__ __forceinline__ void init(const OpDev& op, const float* base_, int col0_, int tid,
-                                       int64_t k_end, int64_t) {
-    base = base_; ld = op.ld; kend = k_end; nb = op.cols; krows = (int)op.rows; ones = op.ones;
-    r = tid & 31; c0 = tid >> 5; col0 = col0_;
-  }
-  __device__ __forceinline__ void load(int64_t k, float (&v)[8]) const {
-    const int64_t kk = k + r;
-    const bool ok = kk < kend;
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const int b = col0 + c0 + 8 * m;
-      float x = 0.f;
-      if (ok && b < nb) x = kk < krows ? base[(int64_t)b * ld + kk] : (kk == ones ? 1.f : 0.f);
-      v[m] = x;
-    }
-  }
-  __device__ __forceinline__ void store(float* lds, const float (&v)[8]) const {
-#pragma unroll
-    for (int m = 0; m < 8; ++m) lds[r * LDP + c0 + 8 * m] = v[m];
-  }
-};
-
 // One 64 (columns i of K1) x 64 (samples b) tile of (Abar K1)^T, squared and summed over
 // i: norm[tile i][b].  A wave's quadrant holds 32 i x 32 b with b along the lanes, so a
 // lane sums its 16 registers, adds the other half-wave's, and the two waves that share
@@ -289,22 +224,20 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_sweep_reduce(OuterArg
   }
 }
 
-static int64_t outer_nA(const kfac_cov_outer_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
+// The V launch alone (kfac_kron_cov_outer_joint forms its own Grams from U and V).
+int cov_launch_outer_v(const OuterArgs& args, int64_t nv, hipStream_t s) {
+  hipLaunchKernelGGL(kfac_cov_outer_v, dim3((unsigned)nv), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}
+
 static int64_t outer_nseg(const kfac_cov_outer_job& j) { return cdiv(j.nG, GSEG); }
 static size_t outer_norm_bytes(const kfac_cov_outer_job& j, int64_t nb) {
   return align_up((size_t)(cdiv(outer_nA(j), TILE) * nb) * sizeof(float), 256);
 }
-static size_t outer_v_bytes(const kfac_cov_outer_job& j, int64_t rows) {
-  return align_up((size_t)rows * (size_t)j.nG * sizeof(float), 256);
-}
 static size_t outer_partial_bytes(const kfac_cov_outer_job& j, int64_t nb, int nc) {
   return align_up((size_t)(nb * outer_nseg(j)) * nc * nc * sizeof(float), 256);
 }
-static bool outer_job_ok(const kfac_cov_outer_job& q) {
-  return q.a && q.D && q.K1 && q.K2 && q.cols > 0 && q.nG > 0 && q.lda >= q.cols &&
-         q.ldD >= q.nG && q.ld1 >= outer_nA(q) && q.ld2 >= q.nG;
-}
-
 }  // namespace kfac
 
 using namespace kfac;
@@ -340,29 +273,14 @@ extern "C" int kfac_kron_cov_outer(const kfac_cov_outer_job* jobs, int njobs, in
   args.nb = nb;
   args.cov = cov;
   int64_t nn = 0, nv = 0, ng = 0;
+  if (!cov_fill_outer(jobs, njobs, nb, rows, args, nn, nv)) return KFAC_EINVAL;
   for (int i = 0; i < njobs; ++i) {
-    const kfac_cov_outer_job& q = jobs[i];
-    if (outer_nA(q) >= lim - TILE) return KFAC_EINVAL;
     OuterJobDev& d = args.job[i];
-    d.a = q.a; d.D = q.D; d.K1 = q.K1; d.K2 = q.K2;
-    d.lda = q.lda; d.ldD = q.ldD; d.ld1 = q.ld1; d.ld2 = q.ld2;
-    d.cols = q.cols;
-    d.ones = q.has_ones ? q.cols : -1;
-    d.nA = (int)outer_nA(q);
-    d.nG = q.nG;
-    d.at = (int)cdiv(d.nA, TILE);
-    d.bt = (int)cdiv(nb, TILE);
-    d.tg = (int)cdiv(q.nG, TILE);
-    d.nseg = (int)outer_nseg(q);
-    d.lower1 = q.lower1 != 0;
-    d.lower2 = q.lower2 != 0;
-    d.vrows = (int)rows;
-    d.n_begin = (int)nn; d.v_begin = (int)nv; d.g_begin = (int)ng;
-    nn += (int64_t)d.at * d.bt;
-    nv += cdiv(rows, TILE) * d.tg;
+    d.nseg = (int)outer_nseg(jobs[i]);
+    d.g_begin = (int)ng;
     ng += nb * d.nseg;
-    if (nn >= lim || nv >= lim || ng >= lim) return KFAC_EINVAL;
-    args.n_end[i] = (int)nn; args.v_end[i] = (int)nv; args.g_end[i] = (int)ng;
+    if (ng >= lim) return KFAC_EINVAL;
+    args.g_end[i] = (int)ng;
   }
   if (!workspace || workspace_bytes < kfac_kron_cov_outer_workspace_bytes(jobs, njobs, nb, nc))
     return KFAC_EWORKSPACE;

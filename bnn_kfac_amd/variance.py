@@ -236,17 +236,8 @@ def _cov_rows(J: Tensor, K: int):
     return J, ld
 
 
-def kron_covariance(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool = True,
-                    max_workspace_bytes: int = 1 << 30) -> Tensor:
-    """cov[b, c, c'] = sum_l J_l[b, c] (K1_l K1_l^T kron K2_l K2_l^T) J_l[b, c']^T.
-
-    terms: [(J_l, K1_l, K2_l)], J (nb, nc, nA*nG) or (nc, nA*nG) in the POSTERIOR's order
-    (posterior_jacobian), K1 (nA x nA), K2 (nG x nG); `lower` marks them lower-triangular
-    (KFAC.invert's Cholesky factors).  Returns (nb, nc, nc) fp32, every block bitwise
-    symmetric.  More than 8 terms fold in groups of 8; the samples are cut into chunks
-    that need at most `max_workspace_bytes` of scratch each (a sample's block depends
-    on that sample only, so chunking does not change a bit).
-    """
+def _cov_jobs(terms, lower: bool, who: str, max_classes: int = None):
+    """(tensors to keep alive, kfac_cov_job tuples, nb, nc) of [(J_l, K1_l, K2_l)]."""
     if not terms:
         raise ValueError("no terms")
     keep, jobs = [], []
@@ -260,8 +251,8 @@ def kron_covariance(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool 
             nb, nc = J3.shape[0], J3.shape[1]
         elif (J3.shape[0], J3.shape[1]) != (nb, nc):
             raise ValueError("all terms need the same (nb, nc)")
-        if nc > MAX_COV_CLASSES:
-            raise ValueError(f"kron_covariance handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        if max_classes is not None and nc > max_classes:
+            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
         for t, what in ((J3, "J"), (K1, "K1"), (K2, "K2")):
             N.require_device(t, what)
         K1c = K1.detach() if K1.stride(-1) == 1 else K1.detach().contiguous()
@@ -269,6 +260,21 @@ def kron_covariance(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool 
         keep.extend([J3, K1c, K2c])
         jobs.append((J3.data_ptr(), ld, nA, nG, K1c.data_ptr(), K1c.stride(0), K2c.data_ptr(),
                      K2c.stride(0), int(lower), int(lower)))
+    return keep, jobs, nb, nc
+
+
+def kron_covariance(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool = True,
+                    max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """cov[b, c, c'] = sum_l J_l[b, c] (K1_l K1_l^T kron K2_l K2_l^T) J_l[b, c']^T.
+
+    terms: [(J_l, K1_l, K2_l)], J (nb, nc, nA*nG) or (nc, nA*nG) in the POSTERIOR's order
+    (posterior_jacobian), K1 (nA x nA), K2 (nG x nG); `lower` marks them lower-triangular
+    (KFAC.invert's Cholesky factors).  Returns (nb, nc, nc) fp32, every block bitwise
+    symmetric.  More than 8 terms fold in groups of 8; the samples are cut into chunks
+    that need at most `max_workspace_bytes` of scratch each (a sample's block depends
+    on that sample only, so chunking does not change a bit).
+    """
+    keep, jobs, nb, nc = _cov_jobs(terms, lower, "kron_covariance", MAX_COV_CLASSES)
     out = torch.empty(nb, nc, nc, dtype=torch.float32, device=keep[0].device)
     if nb == 0:
         return out
@@ -383,19 +389,8 @@ def conv_jacobian_rows(layer: torch.nn.Conv2d, a: Tensor, D: Tensor) -> Tensor:
     return M.reshape(n, nc, -1)
 
 
-def kron_covariance_outer(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]], lower: bool = True,
-                          max_workspace_bytes: int = 1 << 30) -> Tensor:
-    """kron_covariance for Linear layers without their Jacobian rows:
-    cov[b] = sum_l ||K1_l^T abar_l[b]||^2 (D_l[b] K2_l)(D_l[b] K2_l)^T, abar = [a | 1].
-
-    terms: [(a_l, D_l, K1_l, K2_l)] as layer_io_jacobians returns them: a (nb, cols) the
-    layer's input, D (nb, nc, nG) or (nc, nG), K1 (nA x nA) with nA = cols + 1 (bias: the
-    ones column is implicit) or nA = cols, K2 (nG x nG); `lower` marks K1 / K2
-    lower-triangular.  Returns (nb, nc, nc) fp32, every block bitwise symmetric.  More
-    than 8 terms fold in groups of 8; the samples are cut into chunks that need at most
-    `max_workspace_bytes` of scratch each (a sample's block depends on that sample only,
-    so chunking does not change a bit).
-    """
+def _cov_outer_jobs(terms, lower: bool, who: str, max_classes: int = None):
+    """(tensors to keep alive, kfac_cov_outer_job tuples, nb, nc) of [(a_l, D_l, K1_l, K2_l)]."""
     if not terms:
         raise ValueError("no terms")
     keep, jobs = [], []
@@ -418,8 +413,8 @@ def kron_covariance_outer(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]]
             raise ValueError("all terms need the same (nb, nc)")
         if a2.shape[0] != nb:
             raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
-        if nc > MAX_COV_CLASSES:
-            raise ValueError(f"kron_covariance_outer handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        if max_classes is not None and nc > max_classes:
+            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
         if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols):
             a2 = a2.contiguous()
         lda = a2.stride(0) if nb > 1 else cols
@@ -430,6 +425,23 @@ def kron_covariance_outer(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]]
         keep.extend([a2, D3, K1c, K2c])
         jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0,
                      K1c.data_ptr(), K1c.stride(0), K2c.data_ptr(), K2c.stride(0), int(lower), int(lower)))
+    return keep, jobs, nb, nc
+
+
+def kron_covariance_outer(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]], lower: bool = True,
+                          max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance for Linear layers without their Jacobian rows:
+    cov[b] = sum_l ||K1_l^T abar_l[b]||^2 (D_l[b] K2_l)(D_l[b] K2_l)^T, abar = [a | 1].
+
+    terms: [(a_l, D_l, K1_l, K2_l)] as layer_io_jacobians returns them: a (nb, cols) the
+    layer's input, D (nb, nc, nG) or (nc, nG), K1 (nA x nA) with nA = cols + 1 (bias: the
+    ones column is implicit) or nA = cols, K2 (nG x nG); `lower` marks K1 / K2
+    lower-triangular.  Returns (nb, nc, nc) fp32, every block bitwise symmetric.  More
+    than 8 terms fold in groups of 8; the samples are cut into chunks that need at most
+    `max_workspace_bytes` of scratch each (a sample's block depends on that sample only,
+    so chunking does not change a bit).
+    """
+    keep, jobs, nb, nc = _cov_outer_jobs(terms, lower, "kron_covariance_outer", MAX_COV_CLASSES)
     out = torch.empty(nb, nc, nc, dtype=torch.float32, device=keep[0].device)
     if nb == 0:
         return out
@@ -475,7 +487,102 @@ def _glm_chunk_factored(model, layers, inv, x):
     return f, cov
 
 
-def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64, jacobians: str = "dense"):
+def _run_joint(jobs, struct, workspace_bytes, call, nb, nc, device, max_workspace_bytes):
+    """What the two joint calls share: the (nb, nc, nb, nc) result, jobs folded in groups
+    of 8 with `accumulate`, one call over all samples (cross blocks need both samples' rows,
+    so nothing is chunked)."""
+    out = torch.empty(nb * nc, nb * nc, dtype=torch.float32, device=device)
+    if nb > 0:
+        groups = [[struct(*j) for j in jobs[i:i + 8]] for i in range(0, len(jobs), 8)]
+        need = max(workspace_bytes(g, nb, nc) for g in groups)
+        if need == 0:
+            raise ValueError(f"nb = {nb}, nc = {nc}: the joint covariance's {nb * nc} rows exceed one call")
+        if need > max_workspace_bytes:
+            raise ValueError(f"the joint call needs {need} workspace bytes, max_workspace_bytes is "
+                             f"{max_workspace_bytes} (the samples of a joint covariance cannot be chunked)")
+        for gi, g in enumerate(groups):
+            call(g, nb, nc, out, accumulate=gi > 0)
+    return out.view(nb, nc, nb, nc)
+
+
+def kron_covariance_joint(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool = True,
+                          max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance across the samples: cov[b, c, b', c'] =
+    sum_l J_l[b, c] (K1_l K1_l^T kron K2_l K2_l^T) J_l[b', c']^T, the joint (function-space)
+    covariance of all nb*nc outputs of the call.
+
+    terms as kron_covariance takes them; nc has no cap here (nb = 1 gives one sample's full
+    covariance for any number of outputs).  Returns (nb, nc, nb, nc) fp32, a view of the
+    contiguous (nb*nc x nb*nc) matrix, bitwise symmetric: cov[b, c, b', c'] == cov[b', c', b, c];
+    its diagonal blocks cov[b, :, b, :] are kron_covariance's (marginal_blocks).  An entry
+    depends on its two rows only, so the result for a subset of the samples has the bits of
+    those sub-blocks.  More than 8 terms fold in groups of 8.  The samples cannot be
+    chunked: a call that needs more than `max_workspace_bytes` of scratch raises ValueError.
+    """
+    keep, jobs, nb, nc = _cov_jobs(terms, lower, "kron_covariance_joint")
+    return _run_joint(jobs, N.CovJob, N.kron_cov_joint_workspace_bytes, N.kron_cov_joint, nb, nc,
+                      keep[0].device, max_workspace_bytes)
+
+
+def kron_covariance_outer_joint(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]], lower: bool = True,
+                                max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_joint for Linear layers without their Jacobian rows:
+    cov[b, c, b', c'] = sum_l (U_l U_l^T)[b, b'] (V_l V_l^T)[(b, c), (b', c')] with
+    U_l = [a_l | 1] K1_l (nb x nA) and V_l = D_l K2_l (nb*nc x nG).
+
+    terms as kron_covariance_outer takes them; the scratch is U, V and the Gram partials,
+    so a 4097 x 4096 layer is as cheap to hold as a small one.  Returns (nb, nc, nb, nc) fp32
+    with kron_covariance_joint's guarantees (cov[b, c, b', c'] == cov[b', c', b, c] bitwise).
+    """
+    keep, jobs, nb, nc = _cov_outer_jobs(terms, lower, "kron_covariance_outer_joint")
+    return _run_joint(jobs, N.CovOuterJob, N.kron_cov_outer_joint_workspace_bytes, N.kron_cov_outer_joint,
+                      nb, nc, keep[0].device, max_workspace_bytes)
+
+
+def marginal_blocks(cov: Tensor) -> Tensor:
+    """The per-sample blocks cov[b, :, b, :] of a joint covariance (N, nc, N, nc) as
+    (N, nc, nc), what glm_predictive(joint=False) returns and probit_predictive takes.
+    Pure torch."""
+    if cov.dim() != 4 or cov.shape[0] != cov.shape[2] or cov.shape[1] != cov.shape[3]:
+        raise ValueError(f"cov {tuple(cov.shape)}: expected (N, nc, N, nc)")
+    return torch.diagonal(cov, dim1=0, dim2=2).permute(2, 0, 1).contiguous()
+
+
+def _glm_joint(model, layers, inv, x, chunk, jacobians):
+    """glm_predictive(joint=True): Jacobians (dense) or captures (factored) chunk by chunk,
+    concatenated along the samples, then one joint call per route."""
+    logits, dense_rows, captures = [], [[] for _ in layers], [[] for _ in layers]
+    for c0 in range(0, x.shape[0], chunk):
+        xc = x[c0:c0 + chunk]
+        if jacobians == "dense":
+            f, Js = output_jacobians(model, layers, xc)
+            for rows, J in zip(dense_rows, Js):
+                rows.append(J)
+        else:
+            f, io = layer_io_jacobians(model, layers, xc)
+            for li, (layer, (a, D)) in enumerate(zip(layers, io)):
+                if isinstance(layer, torch.nn.Linear):
+                    if a.dim() != 2:
+                        raise ValueError(f"the factored route needs 2-D Linear inputs, got {tuple(a.shape)}")
+                    captures[li].append((a, D))
+                elif isinstance(layer, torch.nn.Conv2d):
+                    dense_rows[li].append(conv_jacobian_rows(layer, a, D))
+                else:
+                    raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
+                                     f"{layer.__class__.__name__}")
+        logits.append(f)
+    outer = [(torch.cat([a for a, _ in cap]), torch.cat([D for _, D in cap]), *inv[layer])
+             for layer, cap in zip(layers, captures) if cap]
+    dense = [(torch.cat(rows), *inv[layer]) for layer, rows in zip(layers, dense_rows) if rows]
+    cov = kron_covariance_outer_joint(outer, lower=True) if outer else None
+    if dense:
+        rows = kron_covariance_joint(dense, lower=True)
+        cov = rows if cov is None else cov + rows
+    return torch.cat(logits), cov
+
+
+def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64, jacobians: str = "dense",
+                   joint: bool = False):
     """The linearised (GLM) predictive of `kfac.model` under the KFAC posterior
     (KFAC.invert's factors, the Gaussian KFAC.sample draws from): (logits (N, nc),
     cov (N, nc, nc)) with cov = sum_l J_l (L_A L_A^T kron L_G L_G^T) J_l^T, in chunks
@@ -484,7 +591,13 @@ def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64, ja
 
     jacobians="dense" materialises every Jacobian row (output_jacobians); "factored"
     takes one layer_io_jacobians call per chunk and never forms a Linear layer's rows
-    (kron_covariance_outer), which is what a wide layer needs."""
+    (kron_covariance_outer), which is what a wide layer needs.
+
+    joint=True returns cov (N, nc, N, nc), the covariance across the samples too (the
+    function-space posterior over x; cov[b, c, b', c'] == cov[b', c', b, c] bitwise): the
+    Jacobians or captures are still taken `chunk` samples at a time, then ONE joint call
+    covers all N (kron_covariance_joint / kron_covariance_outer_joint).  marginal_blocks
+    gives the joint=False result back."""
     if jacobians not in ("dense", "factored"):
         raise ValueError(f"jacobians must be 'dense' or 'factored', got {jacobians!r}")
     model = kfac.model
@@ -492,6 +605,8 @@ def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64, ja
         layers = [m for m in list(model.modules())[1:] if m in kfac.state]
     layers = list(layers)
     inv = kfac.inv_state
+    if joint:
+        return _glm_joint(model, layers, inv, x, chunk, jacobians)
     logits, covs = [], []
     for c0 in range(0, x.shape[0], chunk):
         if jacobians == "factored":

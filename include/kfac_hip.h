@@ -296,6 +296,37 @@ KFAC_API int kfac_kron_cov_outer(const kfac_cov_outer_job* jobs, int njobs, int6
                                  int accumulate, float* cov, void* workspace, size_t workspace_bytes,
                                  kfac_stream_t stream);
 
+/* ----------------------------- GLM predictive covariance, joint across the samples
+ * The calls above stop at the block diagonal.  With rows r = b*nc + c, R = nb*nc, and
+ * T_r = K1^T M_r K2, the joint calls give the whole R x R matrix
+ *   kfac_kron_cov_joint        cov[r][r'] (+)= sum_j < T_{j,r} , T_{j,r'} >_F
+ *   kfac_kron_cov_outer_joint  cov[r][r'] (+)= sum_j S_j[b(r)][b(r')] * W_j[r][r'] ,
+ *                              S_j = U_j U_j^T (U = Abar K1, nb x nA), W_j = V_j V_j^T
+ *                              (V = Delta K2, R x nG): Linear layers, no row formed
+ * (jobs as kfac_cov_job / kfac_cov_outer_job; the diagonal blocks b(r) = b(r') are what
+ * kfac_kron_cov / kfac_kron_cov_outer compute).  cov is R x R with row stride ldc >= R;
+ * columns >= R of a row are not touched.  K (nA*nG, or nA and nG) is cut into 2048-long
+ * segments that depend on K alone; 64x64 tiles of the Grams are summed over a segment in
+ * fp32 (MFMA, exact products, k-ordered), the partials over segments in segment order and
+ * over jobs in job order in fp64, without atomics.  Hence: two calls give identical bits;
+ * the R x R matrix is bitwise symmetric (the lower triangle is computed and mirrored);
+ * diagonal entries are >= 0; and an entry depends on its two rows, the factors and the
+ * job shapes only -- not on nb, nor on where the rows sit in the call -- so the joint
+ * covariance of a subset of the samples has the bits of those sub-blocks of the whole.
+ * accumulate: cov += the sum, else cov = it.  At most 8 jobs per call; nc >= 1 has no
+ * cap (rows are tiled, not classes; nb = 1 gives one sample's full covariance), R and
+ * every launch's task count must fit 31 bits (R <= 2^21).                            */
+KFAC_API size_t kfac_kron_cov_joint_workspace_bytes(const kfac_cov_job* jobs, int njobs, int64_t nb,
+                                                    int nc);
+KFAC_API int kfac_kron_cov_joint(const kfac_cov_job* jobs, int njobs, int64_t nb, int nc, int accumulate,
+                                 float* cov, int64_t ldc, void* workspace, size_t workspace_bytes,
+                                 kfac_stream_t stream);
+KFAC_API size_t kfac_kron_cov_outer_joint_workspace_bytes(const kfac_cov_outer_job* jobs, int njobs,
+                                                          int64_t nb, int nc);
+KFAC_API int kfac_kron_cov_outer_joint(const kfac_cov_outer_job* jobs, int njobs, int64_t nb, int nc,
+                                       int accumulate, float* cov, int64_t ldc, void* workspace,
+                                       size_t workspace_bytes, kfac_stream_t stream);
+
 /* ------------------------------ GLM predictive covariance over a damping grid
  * With A = VA diag(lamA) VA^T and G = VG diag(lamG) VG^T (kfac_syev), kfac_invert's
  * factors satisfy L_A L_A^T = VA diag(wA) VA^T, wA[i] = 1 / (sqrt(s) lamA[i] + sqrt(n)),

@@ -32,6 +32,23 @@ finishes -- C5's eigh() alone takes minutes), for the grid sizes 1, 4, 16 and NT
   loop_ms_per_damping     : loop_ms[16] / 16
   sweep_max_diff_over_max : the sweep against the loop's covariances, max |diff| / max
 all alternated call by call in one session.
+`--joint` instead times the joint covariance across the samples (glm_predictive(joint=True))
+on mlp and basenet15k (both routes) and c5 (factored only; `--workloads` selects, one JSON
+line per workload), per route on the same inputs, alternated call by call:
+  joint_ms      : kron_covariance_joint / kron_covariance_outer_joint alone (factored: the
+                  Linear layers)
+  torch_ms      : the same quantity from torch ops on the same GPU -- dense: T = L_A^T @ M @ L_G
+                  flattened to (nb*nc, nA*nG), sum_l T @ T.mT; factored: (U @ U.mT) expanded
+                  over the classes times V @ V.mT
+  per_sample_ms : kron_covariance / kron_covariance_outer on the same inputs (the block
+                  diagonal alone: what the cross blocks cost on top)
+  glm_joint_ms  : glm_predictive(joint=True) end to end
+  max_diff_vs_torch_over_max : joint call against the torch composition
+and for the dense Gram the algorithmic work kept here: gram_flops = sum_l R (R + 1) K_l (the
+lower triangle with its diagonal, 2 flops per multiply-add), gram_bytes = sum_l 4 R K_l (T
+read once), and what joint_ms makes of them against the 157.3 TF/s fp32-MFMA peak
+(gram_tflops_of_call, a lower bound: the call also runs apply and reduce; a kernel trace of
+`--joint --only cov` gives kfac_cov_joint_gram's own time).
 GPU times are HIP-event times of single calls after a warm-up, medians over `--reps`
 calls.  apply_flops / gram_bytes are the algorithmic work (2 nA^2 nG + 2 nA nG^2 per
 row, halved for the skipped triangle; T read once) for a roofline over kernel times
@@ -51,7 +68,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bnn_kfac_amd import _native as N  # noqa: E402
 from bnn_kfac_amd.curvatures import KFAC  # noqa: E402
 from bnn_kfac_amd.variance import (damping_weights, glm_predictive, glm_predictive_sweep,  # noqa: E402
-                                   kron_covariance, kron_covariance_outer, kron_covariance_outer_sweep,
+                                   kron_covariance, kron_covariance_joint, kron_covariance_outer,
+                                   kron_covariance_outer_joint, kron_covariance_outer_sweep,
                                    kron_covariance_sweep, layer_io_jacobians, output_jacobians)
 
 
@@ -248,16 +266,73 @@ def run_sweep(make, route, dev, args):
     return res
 
 
+PEAK_FP32_MFMA_TFLOPS = 157.3
+
+
+def torch_cov_joint(terms):
+    cov = 0
+    for J, LA, LG in terms:
+        nA, nG = LA.shape[0], LG.shape[0]
+        T = (LA.T @ J.view(-1, nA, nG) @ LG).flatten(1)
+        cov = cov + T @ T.mT
+    return cov
+
+
+def torch_cov_outer_joint(terms):
+    cov = 0
+    for a, D, LA, LG in terms:
+        nc = D.shape[1]
+        abar = torch.cat([a, a.new_ones(a.shape[0], 1)], dim=1) if LA.shape[0] == a.shape[1] + 1 else a
+        U, V = abar @ LA, D.flatten(0, 1) @ LG
+        S = (U @ U.mT).repeat_interleave(nc, dim=0).repeat_interleave(nc, dim=1)
+        cov = cov + S * (V @ V.mT)
+    return cov
+
+
+def run_joint(make, routes, dev, args):
+    net, kfac, layers, x, nb = fit(make, dev)
+    res = {"nb": nb, "layers": [[A.shape[0], G.shape[0]] for A, G in kfac.state.values()]}
+    for route in routes:
+        if route == "dense":
+            _, Js = output_jacobians(net, layers, x)
+            terms = [(J.contiguous(), *kfac.inv_state[l]) for l, J in zip(layers, Js)]
+            joint, composed, per_sample = kron_covariance_joint, torch_cov_joint, kron_covariance
+            R = nb * Js[0].shape[1]
+            r = {"R": R, "gram_flops": sum(R * (R + 1) * t[1].shape[0] * t[2].shape[0] for t in terms),
+                 "gram_bytes": sum(4 * R * t[1].shape[0] * t[2].shape[0] for t in terms)}
+        else:
+            terms = outer_terms(net, kfac, layers, x)
+            joint, composed, per_sample = kron_covariance_outer_joint, torch_cov_outer_joint, kron_covariance_outer
+            r = {"R": nb * terms[0][1].shape[1], "linear_layers": len(terms)}
+        if args.only == "cov":
+            r["joint_ms"] = event_ms(lambda: joint(terms), args.warmup, args.reps)
+        else:
+            r["joint_ms"], r["torch_ms"], r["per_sample_ms"] = alternate_ms(
+                [lambda: joint(terms), lambda: composed(terms), lambda: per_sample(terms)], args.warmup, args.reps)
+            got, want = joint(terms), composed(terms)
+            r["max_diff_vs_torch_over_max"] = float((got.view_as(want) - want).abs().max() / want.abs().max())
+            r["glm_joint_ms"] = event_ms(lambda: glm_predictive(kfac, x, chunk=min(nb, 64), jacobians=route,
+                                                                joint=True), args.warmup, args.reps)
+        if route == "dense":
+            r["gram_tflops_of_call"] = r["gram_flops"] / (r["joint_ms"] * 1e-3) / 1e12
+            r["gram_peak_fraction_of_call"] = r["gram_tflops_of_call"] / PEAK_FP32_MFMA_TFLOPS
+            r["gram_gbytes_per_s_of_call"] = r["gram_bytes"] / (r["joint_ms"] * 1e-3) / 1e9
+        res[route] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="mlp,basenet15k,c5",
-                    help="--sweep: which of mlp, basenet15k, c5 to run (one JSON line each, then the whole)")
+                    help="--sweep / --joint: which of mlp, basenet15k, c5 to run (one JSON line each, then the whole)")
     ap.add_argument("--sweep", type=int, default=0, metavar="NT",
                     help="time the damping grid (glm_predictive_sweep) at 1, 4, 16 and NT dampings instead")
+    ap.add_argument("--joint", action="store_true",
+                    help="time the joint covariance across the samples (glm_predictive(joint=True)) instead")
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", choices=["all", "cov"], default="all",
-                    help="cov: kron_covariance alone (A/B builds, profiler runs)")
+                    help="cov: kron_covariance (--joint: the joint call) alone (A/B builds, profiler runs)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     out = {"workload": "GLM predictive covariance", "lib": N.LIB_PATH}
@@ -267,6 +342,15 @@ def main():
                                   ("c5", c5, "factored")):
             if name in args.workloads.split(","):
                 out[name] = run_sweep(make, route, dev, args)
+                print(json.dumps({name: out[name]}), flush=True)
+        print(json.dumps(out))
+        return
+    if args.joint:
+        out["workload"] = "joint GLM predictive covariance"
+        for name, make, routes in (("mlp", mlp, ("dense", "factored")),
+                                   ("basenet15k", basenet15k, ("dense", "factored")), ("c5", c5, ("factored",))):
+            if name in args.workloads.split(","):
+                out[name] = run_joint(make, routes, dev, args)
                 print(json.dumps({name: out[name]}), flush=True)
         print(json.dumps(out))
         return
