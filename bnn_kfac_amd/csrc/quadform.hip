@@ -113,7 +113,7 @@ extern "C" int kfac_kron_quadform(const kfac_quad_job* jobs, int njobs, int64_t 
                                   kfac_stream_t stream) {
   if (njobs <= 0 || !jobs || nb <= 0 || !out) return KFAC_EINVAL;
   if (njobs > QMAXJ) return KFAC_EINVAL;
-  if (workspace_bytes < kfac_quadform_workspace_bytes(jobs, njobs, nb)) return KFAC_EWORKSPACE;
+  if (!workspace || workspace_bytes < kfac_quadform_workspace_bytes(jobs, njobs, nb)) return KFAC_EWORKSPACE;
   QuadArgs args{};
   args.njobs = njobs;
   args.nb = nb;

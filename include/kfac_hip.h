@@ -215,7 +215,9 @@ KFAC_API int kfac_syev(const kfac_eig_job* jobs, int njobs, void* workspace, siz
  * v[j][b] = J_jb kron(K1_j, K2_j) J_jb^T without forming the Kronecker product:
  * with M = J_jb viewed (nA x nG) row-major (the reference's flat order
  * a*nG + g), v = <K1^T M, M K2^T>_F.  K1/K2 may be flagged lower-triangular
- * (Cholesky factors) to skip their zero blocks.
+ * (Cholesky factors) to skip their zero blocks: a flagged factor must hold zeros
+ * in its upper triangle, since only the tiles strictly above the diagonal tiles
+ * are skipped and the diagonal tiles are read in full.
  * out[b] = sum_j |v[j][b]| if abs_sum else sum_j v[j][b].
  * Replaces classification_ll_block.py:126-132 (torch.kron + J H J^T) and
  * regression_ll_block.py:128-139 (kronecker_product + J H J^T).          */
