@@ -78,6 +78,11 @@ class CovOuterJob(ctypes.Structure):
                 ("K2", c_vp), ("ld2", c_i64), ("lower1", c_i32), ("lower2", c_i32)]
 
 
+class CovConvRowsJob(ctypes.Structure):
+    _fields_ = [("x", Operand), ("D", c_vp), ("ldD", c_i64), ("nG", c_i32), ("reserved", c_i32),
+                ("M", c_vp), ("ldM", c_i64)]
+
+
 class CovSweepJob(ctypes.Structure):
     _fields_ = [("J", c_vp), ("ldJ", c_i64), ("nA", c_i32), ("nG", c_i32), ("VA", c_vp),
                 ("ldA", c_i64), ("VG", c_vp), ("ldG", c_i64), ("wA", c_vp), ("ldwA", c_i64),
@@ -152,6 +157,8 @@ SIGNATURES = {
                                                               c_i64, ctypes.c_int]),
     "kfac_kron_cov_outer": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
                                            ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_cov_conv_rows": (ctypes.c_int, [ctypes.POINTER(CovConvRowsJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                          c_vp]),
     "kfac_kron_cov_joint_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64,
                                                               ctypes.c_int]),
     "kfac_kron_cov_joint": (ctypes.c_int, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64, ctypes.c_int,
@@ -510,6 +517,23 @@ def kron_cov_outer(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool =
     ws = workspace.get(out.device, need)
     check(L.kfac_kron_cov_outer(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
                                 stream_handle(out.device)), "kfac_kron_cov_outer")
+
+
+def cov_conv_rows_job(x: Operand, D: torch.Tensor, ldD: int, nG: int, M: torch.Tensor, ldM: int) -> CovConvRowsJob:
+    """One Conv2d layer of kfac_cov_conv_rows: x the PATCH operand of its input (patch_operand),
+    D its output Jacobian with rows (b, c) ldD apart, M the rows to write, ldM apart."""
+    require_device(D, "D")
+    require_device(M, "M")
+    return CovConvRowsJob(x, D.data_ptr(), ldD, nG, 0, M.data_ptr(), ldM)
+
+
+def cov_conv_rows(jobs, nb: int, nc: int, device: torch.device = None) -> None:
+    """kfac_cov_conv_rows on torch's current stream of `device` (default: the current
+    device): Conv2d Jacobian rows M[b, c] = unfold(a_b) D[b, c]^T, <= 8 jobs per call."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    check(lib().kfac_cov_conv_rows(as_array(CovConvRowsJob, jobs), len(jobs), nb, nc,
+                                   stream_handle(device)), "kfac_cov_conv_rows")
 
 
 def kron_cov_joint_workspace_bytes(jobs, nb: int, nc: int) -> int:

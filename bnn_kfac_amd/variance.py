@@ -389,6 +389,70 @@ def conv_jacobian_rows(layer: torch.nn.Conv2d, a: Tensor, D: Tensor) -> Tensor:
     return M.reshape(n, nc, -1)
 
 
+def _conv_rows_uncovered(layer: torch.nn.Conv2d):
+    """Why kfac_cov_conv_rows does not cover `layer` (None: it does)."""
+    if tuple(layer.dilation) != (1, 1):
+        return f"dilation {tuple(layer.dilation)}"
+    if layer.groups != 1:
+        return f"groups {layer.groups}"
+    if layer.padding_mode != "zeros":
+        return f"padding_mode {layer.padding_mode!r}"
+    if isinstance(layer.padding, str):
+        return f"padding {layer.padding!r}"
+    return None
+
+
+def conv_jacobian_rows_device(layer: torch.nn.Conv2d, a: Tensor, D: Tensor) -> Tensor:
+    """conv_jacobian_rows by one device launch (kfac_cov_conv_rows): the im2col stays
+    implicit, the classes share one GEMM per sample, the bias row is the ones column.
+    a (n, C, H, W) and D (n, nc, Cout, Ho, Wo) fp32 on a HIP device; returns (n, nc, nA*nG)
+    fp32 in the posterior's order.  a may be a batch view (sample stride >= C*H*W, the
+    inner dimensions contiguous) and D may have padded rows (row stride >= nG*L): neither is
+    copied; anything else is.  Two calls give identical bits and a row depends on its own
+    a_b, D[b, c] only.  Raises ValueError for what the kernel does not cover: dilation != 1,
+    groups != 1, padding_mode != "zeros", string padding."""
+    why = _conv_rows_uncovered(layer)
+    if why is not None:
+        raise ValueError(f"conv_jacobian_rows_device does not cover {why}; use conv_jacobian_rows")
+    a, D = a.detach(), D.detach()
+    if a.dim() != 4 or D.dim() != 5 or D.shape[0] != a.shape[0]:
+        raise ValueError(f"a {tuple(a.shape)} / D {tuple(D.shape)}: expected (n, C, H, W) and "
+                         f"(n, nc, Cout, Ho, Wo)")
+    N.require_device(a, "a", layer)
+    N.require_device(D, "D", layer)
+    n, C, H, W = a.shape
+    nc, nG = D.shape[1], D.shape[2]
+    if C != layer.in_channels or nG != layer.out_channels:
+        raise ValueError(f"a {tuple(a.shape)} / D {tuple(D.shape)} do not fit {layer}")
+    nA = C * layer.kernel_size[0] * layer.kernel_size[1] + (layer.bias is not None)
+    M = torch.empty(n, nc, nA * nG, dtype=torch.float32, device=a.device)
+    if n == 0 or nc == 0:
+        return M
+    if not a[0].is_contiguous() or (n > 1 and a.stride(0) < C * H * W):
+        a = a.contiguous()
+    op = N.patch_operand(a[:1], layer.kernel_size, layer.padding, layer.stride, layer.bias is not None)
+    L = op.L
+    if (D.shape[3], D.shape[4]) != (op.Ho, op.Wo):
+        raise ValueError(f"D {tuple(D.shape)}: {layer} maps a {tuple(a.shape)} to {op.Ho} x {op.Wo} positions")
+    if D[0, 0].is_contiguous():  # D[b, c] is one nG*L block: a view, whatever the outer strides
+        D3 = D.as_strided((n, nc, nG * L), (D.stride(0), D.stride(1), 1))
+    else:
+        D3 = D.contiguous().view(n, nc, nG * L)
+    D3, ldD = _cov_rows(D3, nG * L)
+    op.rows = n * L
+    op.sB = a.stride(0) if n > 1 else C * H * W
+    N.cov_conv_rows([N.cov_conv_rows_job(op, D3, ldD, nG, M, nA * nG)], n, nc, a.device)
+    return M
+
+
+def _conv_rows(layer: torch.nn.Conv2d, a: Tensor, D: Tensor) -> Tensor:
+    """The factored route's Conv2d rows: on the device where kfac_cov_conv_rows covers the
+    layer, from torch (conv_jacobian_rows) where it does not."""
+    if _conv_rows_uncovered(layer) is None:
+        return conv_jacobian_rows_device(layer, a, D)
+    return conv_jacobian_rows(layer, a, D)
+
+
 def _cov_outer_jobs(terms, lower: bool, who: str, max_classes: int = None):
     """(tensors to keep alive, kfac_cov_outer_job tuples, nb, nc) of [(a_l, D_l, K1_l, K2_l)]."""
     if not terms:
@@ -467,7 +531,8 @@ def kron_covariance_outer(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]]
 
 def _glm_chunk_factored(model, layers, inv, x):
     """One chunk of the factored route: Linear layers by kron_covariance_outer, Conv2d
-    layers by kron_covariance on rows built from the same captures; the two are added."""
+    layers by kron_covariance on rows formed from the same captures (_conv_rows: on the
+    device for every layer kfac_cov_conv_rows covers); the two are added."""
     f, io = layer_io_jacobians(model, layers, x)
     outer, dense = [], []
     for layer, (a, D) in zip(layers, io):
@@ -476,7 +541,7 @@ def _glm_chunk_factored(model, layers, inv, x):
                 raise ValueError(f"the factored route needs 2-D Linear inputs, got {tuple(a.shape)}")
             outer.append((a, D, *inv[layer]))
         elif isinstance(layer, torch.nn.Conv2d):
-            dense.append((conv_jacobian_rows(layer, a, D), *inv[layer]))
+            dense.append((_conv_rows(layer, a, D), *inv[layer]))
         else:
             raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
                              f"{layer.__class__.__name__}")
@@ -566,7 +631,7 @@ def _glm_joint(model, layers, inv, x, chunk, jacobians):
                         raise ValueError(f"the factored route needs 2-D Linear inputs, got {tuple(a.shape)}")
                     captures[li].append((a, D))
                 elif isinstance(layer, torch.nn.Conv2d):
-                    dense_rows[li].append(conv_jacobian_rows(layer, a, D))
+                    dense_rows[li].append(_conv_rows(layer, a, D))
                 else:
                     raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
                                      f"{layer.__class__.__name__}")
@@ -591,7 +656,8 @@ def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64, ja
 
     jacobians="dense" materialises every Jacobian row (output_jacobians); "factored"
     takes one layer_io_jacobians call per chunk and never forms a Linear layer's rows
-    (kron_covariance_outer), which is what a wide layer needs.
+    (kron_covariance_outer), which is what a wide layer needs; a Conv2d layer's rows come
+    from the same captures in one device launch (conv_jacobian_rows_device).
 
     joint=True returns cov (N, nc, N, nc), the covariance across the samples too (the
     function-space posterior over x; cov[b, c, b', c'] == cov[b', c', b, c] bitwise): the
@@ -817,7 +883,8 @@ def glm_predictive_sweep(kfac, x: Tensor, dampings, layers: Iterable = None, chu
     grid; each grid point costs one weighted contraction.  Uses `kfac.eig_state`, calling
     `kfac.eigh()` when nothing is cached.  `jacobians` as in glm_predictive: "factored" sends
     Linear layers through kron_covariance_outer_sweep and Conv2d layers through
-    kron_covariance_sweep on conv_jacobian_rows."""
+    kron_covariance_sweep on their rows (conv_jacobian_rows_device where the kernel covers the
+    layer, conv_jacobian_rows otherwise)."""
     if jacobians not in ("dense", "factored"):
         raise ValueError(f"jacobians must be 'dense' or 'factored', got {jacobians!r}")
     model = kfac.model
@@ -847,7 +914,7 @@ def glm_predictive_sweep(kfac, x: Tensor, dampings, layers: Iterable = None, chu
                         raise ValueError(f"the factored route needs 2-D Linear inputs, got {tuple(a.shape)}")
                     outer.append((a, D, *basis[layer]))
                 elif isinstance(layer, torch.nn.Conv2d):
-                    dense.append((conv_jacobian_rows(layer, a, D), *basis[layer]))
+                    dense.append((_conv_rows(layer, a, D), *basis[layer]))
                 else:
                     raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
                                      f"{layer.__class__.__name__}")

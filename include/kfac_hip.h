@@ -271,8 +271,10 @@ KFAC_API int kfac_kron_cov(const kfac_cov_job* jobs, int njobs, int64_t nb, int 
  * (K1^T abar_b)(K2^T delta_{b,c})^T and
  *   cov[b] (+)= sum_j s_j[b] * V_{j,b} V_{j,b}^T ,
  *   s_j[b] = || K1_j^T abar_{j,b} ||^2 ,   V_{j,b} = Delta_{j,b} K2_j   (nc x nG),
- * Delta_{j,b} the nc rows delta_{b,c}.  Only row-major (Linear) inputs are covered: a
- * Conv2d layer's row is a sum over positions and goes through kfac_kron_cov.
+ * Delta_{j,b} the nc rows delta_{b,c}.  These jobs take row-major (Linear) inputs.  A
+ * Conv2d layer's row is a sum over positions, not rank one: kfac_cov_conv_rows (below)
+ * forms its rows on the device from the same (input, output Jacobian) pair, and they go
+ * through kfac_kron_cov / kfac_kron_cov_sweep / kfac_kron_cov_joint as kfac_cov_job::J.
  * s_j[b] is summed over 64-column tiles of abar K1 in tile order, V V^T over K segments
  * in segment order, the jobs in job order, all in fp64 and without atomics: two calls
  * give identical bits, a sample's block depends on that sample only, and every nc x nc
@@ -297,6 +299,35 @@ KFAC_API size_t kfac_kron_cov_outer_workspace_bytes(const kfac_cov_outer_job* jo
 KFAC_API int kfac_kron_cov_outer(const kfac_cov_outer_job* jobs, int njobs, int64_t nb, int nc,
                                  int accumulate, float* cov, void* workspace, size_t workspace_bytes,
                                  kfac_stream_t stream);
+
+/* ------------------------------- Conv2d Jacobian rows for the GLM predictive
+ * The rows kfac_cov_job::J wants, for a Conv2d layer, from the pair the factored route
+ * captures: the layer's input a (nb images C x H x W, x.sB apart; x is a KFAC_PATCH
+ * operand over all nb*L positions, its ones column the bias row) and D, the Jacobian of
+ * the outputs at the layer's output, D_{b,c} (nG x L, L = Ho*Wo) at D + (b*nc + c)*ldD:
+ *   M_{b,c}[k][g]    = sum_p patch_b[p][k] * D_{b,c}[g][p]     (k < cols, F.unfold's order)
+ *   M_{b,c}[cols][g] = sum_p D_{b,c}[g][p]                     (has_ones: the bias row)
+ * written at M + (b*nc + c)*ldM, element k*nG + g, nA = cols + has_ones: the POSTERIOR's
+ * order.  Only those nA*nG elements of each row are written.  One launch, no workspace:
+ * per sample one fp32-MFMA GEMM over all nc*nG columns, an element one k-ordered fma chain
+ * over the sample's positions (no split-K, no atomics).  Hence two calls give identical
+ * bits, and a row depends on a_b, D_{b,c} and the shapes only: not on nb, not on nc, not on
+ * where its columns fall among the tiles.  Zero padding, dilation 1, groups 1.  At most 8
+ * jobs per call, nc >= 1 has no cap; kh, kw < 2^15, C*H*W < 2^31, x.sB >= C*H*W,
+ * ldD >= nG*L, ldM >= nA*nG, every patch inside the padded image, x.rows = nb*L; nb,
+ * nc*nG and the task count (nb x 64-row tiles x 64-column tiles, summed over the jobs)
+ * must fit 31 bits.                                                               */
+typedef struct kfac_cov_conv_rows_job {
+  kfac_operand x; /* layout KFAC_PATCH, rows = nb*L */
+  const float* D;
+  int64_t ldD;
+  int32_t nG, reserved;
+  float* M;
+  int64_t ldM;
+} kfac_cov_conv_rows_job;
+
+KFAC_API int kfac_cov_conv_rows(const kfac_cov_conv_rows_job* jobs, int njobs, int64_t nb, int nc,
+                                kfac_stream_t stream);
 
 /* ----------------------------- GLM predictive covariance, joint across the samples
  * The calls above stop at the block diagonal.  With rows r = b*nc + c, R = nb*nc, and

@@ -49,6 +49,16 @@ lower triangle with its diagonal, 2 flops per multiply-add), gram_bytes = sum_l 
 read once), and what joint_ms makes of them against the 157.3 TF/s fp32-MFMA peak
 (gram_tflops_of_call, a lower bound: the call also runs apply and reduce; a kernel trace of
 `--joint --only cov` gives kfac_cov_joint_gram's own time).
+`--conv-rows` instead times the Conv2d rows of the factored route on basenet15k (nb = 256) and
+on LeNet-5 (conv 1->6 with padding 2 and 6->16, 5x5 kernels; nb = 64), nc = 10, on one
+layer_io_jacobians capture, alternated call by call:
+  rows_device_ms / rows_torch_ms : conv_jacobian_rows_device (kfac_cov_conv_rows) against
+                  conv_jacobian_rows (unfold + einsum + cat) for all conv layers, and per layer
+                  under conv_layers with the launch's task count
+  rows_device_tflops : 2 nA nG L flops per row over rows_device_ms
+  glm_factored_device_rows_ms / glm_factored_torch_rows_ms / glm_dense_ms : glm_predictive end
+                  to end, factored with either rows (torch's rows: the route before the device
+                  rows existed) and dense
 GPU times are HIP-event times of single calls after a warm-up, medians over `--reps`
 calls.  apply_flops / gram_bytes are the algorithmic work (2 nA^2 nG + 2 nA nG^2 per
 row, halved for the skipped triangle; T read once) for a roofline over kernel times
@@ -66,6 +76,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bnn_kfac_amd import _native as N  # noqa: E402
+from bnn_kfac_amd import variance as V  # noqa: E402
 from bnn_kfac_amd.curvatures import KFAC  # noqa: E402
 from bnn_kfac_amd.variance import (damping_weights, glm_predictive, glm_predictive_sweep,  # noqa: E402
                                    kron_covariance, kron_covariance_joint, kron_covariance_outer,
@@ -321,6 +332,61 @@ def run_joint(make, routes, dev, args):
     return res
 
 
+def lenet5():
+    return nn.Sequential(nn.Conv2d(1, 6, 5, padding=2), nn.ReLU(), nn.MaxPool2d(2), nn.Conv2d(6, 16, 5), nn.ReLU(),
+                         nn.MaxPool2d(2), nn.Flatten(), nn.Linear(400, 120), nn.ReLU(), nn.Linear(120, 84),
+                         nn.ReLU(), nn.Linear(84, 10)), (1, 28, 28), 64
+
+
+def run_conv_rows(make, dev, args):
+    """The Conv2d rows of the factored route: the device call against torch's rows on the same
+    captures, then glm_predictive end to end three ways, alternated call by call -- factored
+    with the device rows, factored with torch's rows (the route as it was before the device
+    rows: variance._conv_rows pointed at conv_jacobian_rows) and dense."""
+    net, kfac, layers, x, nb = fit(make, dev)
+    _, io = layer_io_jacobians(net, layers, x)
+    convs = [(l, a, D) for l, (a, D) in zip(layers, io) if isinstance(l, nn.Conv2d)]
+    nc = convs[0][2].shape[1]
+    res = {"nb": nb, "nc": nc, "conv_layers": []}
+    flops = 0
+    for l, a, D in convs:
+        nA = l.in_channels * l.kernel_size[0] * l.kernel_size[1] + (l.bias is not None)
+        nG, L = D.shape[2], D.shape[3] * D.shape[4]
+        flops += 2 * nA * nG * L * nb * nc
+        dev_ms, torch_ms = alternate_ms([lambda: V.conv_jacobian_rows_device(l, a, D),
+                                         lambda: V.conv_jacobian_rows(l, a, D)], args.warmup, args.reps)
+        got, want = V.conv_jacobian_rows_device(l, a, D), V.conv_jacobian_rows(l, a, D)
+        res["conv_layers"].append({"nA": nA, "nG": nG, "L": L, "tasks": nb * -(-nA // 64) * -(-nc * nG // 64),
+                                   "rows_device_ms": dev_ms, "rows_torch_ms": torch_ms,
+                                   "max_diff_over_max": float((got - want).abs().max() / want.abs().max())})
+    res["rows_flops"] = flops
+    res["rows_device_ms"], res["rows_torch_ms"] = alternate_ms(
+        [lambda: [V.conv_jacobian_rows_device(l, a, D) for l, a, D in convs],
+         lambda: [V.conv_jacobian_rows(l, a, D) for l, a, D in convs]], args.warmup, args.reps)
+    res["rows_device_tflops"] = flops / (res["rows_device_ms"] * 1e-3) / 1e12
+    if args.only == "cov":
+        return res
+    device_rows = V._conv_rows
+
+    def factored(rows):
+        def call():
+            V._conv_rows = rows
+            try:
+                return glm_predictive(kfac, x, chunk=nb, jacobians="factored")
+            finally:
+                V._conv_rows = device_rows
+        return call
+
+    res["glm_factored_device_rows_ms"], res["glm_factored_torch_rows_ms"], res["glm_dense_ms"] = alternate_ms(
+        [factored(device_rows), factored(V.conv_jacobian_rows), lambda: glm_predictive(kfac, x, chunk=nb)],
+        args.warmup, args.reps)
+    new, old = factored(device_rows)()[1], factored(V.conv_jacobian_rows)()[1]
+    dense = glm_predictive(kfac, x, chunk=nb)[1]
+    res["device_vs_torch_rows_max_diff_over_max"] = float((new - old).abs().max() / old.abs().max())
+    res["factored_vs_dense_max_diff_over_max"] = float((new - dense).abs().max() / dense.abs().max())
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="mlp,basenet15k,c5",
@@ -329,6 +395,9 @@ def main():
                     help="time the damping grid (glm_predictive_sweep) at 1, 4, 16 and NT dampings instead")
     ap.add_argument("--joint", action="store_true",
                     help="time the joint covariance across the samples (glm_predictive(joint=True)) instead")
+    ap.add_argument("--conv-rows", action="store_true",
+                    help="time the Conv2d rows of the factored route (conv_jacobian_rows_device against torch's "
+                         "rows, glm_predictive end to end with either and dense) on basenet15k and lenet5 instead")
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", choices=["all", "cov"], default="all",
@@ -336,6 +405,13 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     out = {"workload": "GLM predictive covariance", "lib": N.LIB_PATH}
+    if args.conv_rows:
+        out["workload"] = "Conv2d Jacobian rows of the factored GLM predictive"
+        for name, make in (("basenet15k", basenet15k), ("lenet5", lenet5)):
+            out[name] = run_conv_rows(make, dev, args)
+            print(json.dumps({name: out[name]}), flush=True)
+        print(json.dumps(out))
+        return
     if args.sweep:
         out["workload"] = "GLM predictive over a damping grid"
         for name, make, route in (("mlp", mlp, "factored"), ("basenet15k", basenet15k, "dense"),
