@@ -96,6 +96,17 @@ class CovOuterSweepJob(ctypes.Structure):
                 ("ldwG", c_i64)]
 
 
+class CovFullJob(ctypes.Structure):
+    _fields_ = [("J", c_vp), ("ldJ", c_i64), ("nA", c_i32), ("nG", c_i32), ("VA", c_vp),
+                ("ldA", c_i64), ("VG", c_vp), ("ldG", c_i64), ("W", c_vp), ("ldW", c_i64)]
+
+
+class CovOuterFullJob(ctypes.Structure):
+    _fields_ = [("a", c_vp), ("lda", c_i64), ("cols", c_i32), ("has_ones", c_i32), ("D", c_vp),
+                ("ldD", c_i64), ("nG", c_i32), ("reserved", c_i32), ("VA", c_vp), ("ldA", c_i64),
+                ("VG", c_vp), ("ldG", c_i64), ("W", c_vp), ("ldW", c_i64)]
+
+
 class SampleJob(ctypes.Structure):
     _fields_ = [("LA", c_vp), ("ldA", c_i64), ("LG", c_vp), ("ldG", c_i64), ("Z", c_vp),
                 ("nA", c_i32), ("nG", c_i32), ("W", c_vp), ("ldW", c_i64), ("bias", c_vp),
@@ -178,6 +189,16 @@ SIGNATURES = {
     "kfac_kron_cov_outer_sweep": (ctypes.c_int, [ctypes.POINTER(CovOuterSweepJob), ctypes.c_int, c_i64,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                                  ctypes.c_size_t, c_vp]),
+    "kfac_kron_cov_full_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovFullJob), ctypes.c_int,
+                                                             c_i64, ctypes.c_int, ctypes.c_int]),
+    "kfac_kron_cov_full": (ctypes.c_int, [ctypes.POINTER(CovFullJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_kron_cov_outer_full_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovOuterFullJob),
+                                                                   ctypes.c_int, c_i64, ctypes.c_int,
+                                                                   ctypes.c_int]),
+    "kfac_kron_cov_outer_full": (ctypes.c_int, [ctypes.POINTER(CovOuterFullJob), ctypes.c_int, c_i64,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                                ctypes.c_size_t, c_vp]),
     "kfac_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SampleJob), ctypes.c_int]),
     "kfac_sample": (ctypes.c_int, [ctypes.POINTER(SampleJob), ctypes.c_int, ctypes.c_int, c_vp,
                                    ctypes.c_size_t, c_vp]),
@@ -606,6 +627,36 @@ def kron_cov_outer_sweep(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, acc
     ws = workspace.get(out.device, need)
     check(L.kfac_kron_cov_outer_sweep(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws),
                                       ws.numel(), stream_handle(out.device)), "kfac_kron_cov_outer_sweep")
+
+
+def kron_cov_full_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
+    return lib().kfac_kron_cov_full_workspace_bytes(as_array(CovFullJob, jobs), len(jobs), nb, nc, nt)
+
+
+def kron_cov_full(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_kron_cov_full: out (nt, nb, nc, nc) (+)= the per-entry weighted Grams, <= 8 jobs, nt <= 64."""
+    L = lib()
+    arr = as_array(CovFullJob, jobs)
+    need = L.kfac_kron_cov_full_workspace_bytes(arr, len(jobs), nb, nc, nt)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_kron_cov_full(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws), ws.numel(),
+                               stream_handle(out.device)), "kfac_kron_cov_full")
+
+
+def kron_cov_outer_full_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
+    return lib().kfac_kron_cov_outer_full_workspace_bytes(as_array(CovOuterFullJob, jobs), len(jobs),
+                                                          nb, nc, nt)
+
+
+def kron_cov_outer_full(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_kron_cov_outer_full: out (nt, nb, nc, nc) (+)= Q diag(r) Q^T per grid point, <= 8 jobs,
+    nt <= 64."""
+    L = lib()
+    arr = as_array(CovOuterFullJob, jobs)
+    need = L.kfac_kron_cov_outer_full_workspace_bytes(arr, len(jobs), nb, nc, nt)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_kron_cov_outer_full(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws),
+                                     ws.numel(), stream_handle(out.device)), "kfac_kron_cov_outer_full")
 
 
 def sample(jobs, device: torch.device, accumulate: bool) -> None:

@@ -182,7 +182,7 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_sweep_gram(CovArgs args, Sw
   const int seg = (int)(local % C.nseg);
   const int nc = args.nc;
   const int64_t K = (int64_t)C.nA * C.nG;
-  cov_wgram_segment<true>(C.T + b * nc * K, K, nc, (int64_t)seg * WSEG, sw.job[j], C.nG, sw.ntau,
+  cov_wgram_segment<WGRAM_RANK1>(C.T + b * nc * K, K, nc, (int64_t)seg * WSEG, sw.job[j], C.nG, sw.ntau,
                           C.partial + local * nc * nc, args.nb * C.nseg * nc * nc, lds);
 }
 
@@ -213,6 +213,14 @@ int cov_launch_apply(const CovArgs& args, hipStream_t s) {
   hipLaunchKernelGGL(kfac_cov_apply_u, dim3((unsigned)args.nu), dim3(NTHREADS), 0, s, args);
   KFAC_CHECK_LAUNCH();
   hipLaunchKernelGGL(kfac_cov_apply_t, dim3((unsigned)args.nt), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}
+
+// The sweep reduce alone (covariance_full.hip forms its own weighted Gram partials).
+int cov_launch_sweep_reduce(const CovArgs& args, int ntau, hipStream_t s) {
+  hipLaunchKernelGGL(kfac_cov_sweep_reduce, dim3((unsigned)args.nb, (unsigned)ntau), dim3(NTHREADS), 0, s,
+                     args);
   KFAC_CHECK_LAUNCH();
   return KFAC_OK;
 }

@@ -96,7 +96,7 @@ static_assert(WGRAM_LDS * sizeof(float) <= 65536, "static LDS");
 
 struct SweepWeights {
   const float* wA;  // nt x nA, row tau at wA + tau*ldwA
-  const float* wG;  // nt x nG
+  const float* wG;  // nt x nG (WGRAM_FLAT: nt x nA*nG, the per-entry weights)
   int64_t ldwA, ldwG;
 };
 struct SweepArgs {
@@ -107,7 +107,10 @@ struct SweepArgs {
 // Weighted Gram partials of one sample over the K segment [k0, k0 + WSEG): for every grid
 // point tau, part[tau * part_stride] (nc x nc, lower triangle written) =
 //   sum_k w_tau[k] Tb[c][k] Tb[c'][k] ,
-//   w_tau[k] = wA_tau[k / nG] * wG_tau[k % nG] (DENSE)  or  wG_tau[k] (K = nG).
+//   w_tau[k] = wA_tau[k / nG] * wG_tau[k % nG] (WGRAM_RANK1: K = nA*nG),
+//              wG_tau[k]                        (WGRAM_VECTOR: K = nG), or
+//              W_tau[k], W_tau = wG + tau*ldwG  (WGRAM_FLAT: K = nA*nG, one weight per
+//              entry in the rows' own flat order; wA unused: no division, no product).
 // The sample's nc row segments are staged ONCE ([k][c], thread t owns k0 + t and its
 // (a, g): one division per thread, none in a loop); the grid points then go through in
 // groups of WTG on the staged data: a group's weights are staged beside the segment, and
@@ -115,7 +118,9 @@ struct SweepArgs {
 // (the B fragment scaled by its k-row's weight: one multiply per MFMA and tau), so slice
 // tau does not depend on nt or on its place in the group.  The four wave partials are
 // summed in cov_gram_segment's fixed order.  Loads are unconditional (clamped index).
-template <bool DENSE>
+enum WGramMode { WGRAM_VECTOR = 0, WGRAM_RANK1 = 1, WGRAM_FLAT = 2 };
+
+template <WGramMode MODE>
 __device__ __forceinline__ void cov_wgram_segment(const float* Tb, int64_t K, int nc, int64_t k0,
                                                   const SweepWeights& W, int nG, int nt, float* part,
                                                   int64_t part_stride, float* lds) {
@@ -133,7 +138,7 @@ __device__ __forceinline__ void cov_wgram_segment(const float* Tb, int64_t K, in
     xs[tid * WPITCH + c] = (live && c < nc) ? x : 0.f;
   }
   int64_t ia = 0, ig = kc;
-  if (DENSE) {
+  if (MODE == WGRAM_RANK1) {
     ia = kc / nG;
     ig = kc - ia * nG;
   }
@@ -145,7 +150,7 @@ __device__ __forceinline__ void cov_wgram_segment(const float* Tb, int64_t K, in
     for (int t = 0; t < WTG; ++t) {
       const int64_t tt = min(t0 + t, nt - 1);
       float w = W.wG[tt * W.ldwG + ig];
-      if (DENSE) w *= W.wA[tt * W.ldwA + ia];
+      if (MODE == WGRAM_RANK1) w *= W.wA[tt * W.ldwA + ia];
       wl[t * WSEG + tid] = live ? w : 0.f;
     }
     __syncthreads();  // (the first pass: the segment too)
@@ -233,6 +238,9 @@ static_assert(sizeof(OuterArgs) <= 4096, "kernel argument block");
 // all rows of every job; kfac_cov_outer_v (covariance_outer.hip): V = Delta K2.
 int cov_launch_apply(const CovArgs& args, hipStream_t s);
 int cov_launch_outer_v(const OuterArgs& args, int64_t nv, hipStream_t s);
+// kfac_cov_sweep_reduce (covariance.hip) on a block whose njobs, nc, nb, accumulate, cov and
+// the jobs' partial (ntau x nb x nseg x nc*nc) / nseg are filled.
+int cov_launch_sweep_reduce(const CovArgs& args, int ntau, hipStream_t s);
 
 constexpr int KFAC_SAMPLEROWS = 17;  // panel layout of Abar^T (internal to the outer routes)
 

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_sweep_gram(OuterArgs 
   const int seg = (int)(local % C.nseg);
   const int nc = args.nc;
   const int64_t K = C.nG;
-  cov_wgram_segment<false>(C.V + b * nc * K, K, nc, (int64_t)seg * WSEG, sw.job[jb], C.nG, sw.ntau,
+  cov_wgram_segment<WGRAM_VECTOR>(C.V + b * nc * K, K, nc, (int64_t)seg * WSEG, sw.job[jb], C.nG, sw.ntau,
                            C.partial + local * nc * nc, args.nb * C.nseg * nc * nc, lds);
 }
 

@@ -953,6 +953,257 @@ def log_det_sweep(eig_state, dampings) -> Tensor:
     return out
 
 
+# ------------------------------------------------- per-entry eigenbasis weights (EFB)
+# EFB keeps the KFAC eigenbases and refits every one of the nA*nG eigenvalues: EFB.sample draws
+# S = V_A (Z o Lambda^-T) V_G^T with Lambda^- = inv_state (nG x nA) = (s lam + n)^(-1/2), so
+# cov = sum_layers sum_{i,g} W[i][g] Y[i][g] Y'[i][g] with W = (Lambda^-)^T squared: the sweep
+# calls' contraction with an arbitrary weight per (i, g) (kfac_kron_cov_full,
+# kfac_kron_cov_outer_full).  A damping grid costs no inversion and no eigendecomposition.
+def _full_shapes(VA: Tensor, VG: Tensor, W: Tensor):
+    """(nA, nG, W as (nt, nA, nG)) after the shape checks, which need no device."""
+    for V, what in ((VA, "VA"), (VG, "VG")):
+        if V.dim() != 2 or V.shape[0] != V.shape[1]:
+            raise ValueError(f"{what} {tuple(V.shape)}: expected a square matrix of eigenvectors")
+    nA, nG = VA.shape[0], VG.shape[0]
+    W = W.detach()
+    if W.dim() == 2:
+        W = W.unsqueeze(0)
+    if W.dim() != 3 or tuple(W.shape[1:]) != (nA, nG):
+        raise ValueError(f"W {tuple(W.shape)}: expected (nt, {nA}, {nG}) or ({nA}, {nG})")
+    return nA, nG, W
+
+
+def _full_weights(W: Tensor):
+    """(W (nt, nA, nG) with its matrices contiguous blocks, the stride between them)."""
+    N.require_device(W, "W")
+    nt, nA, nG = W.shape
+    if not W[0].is_contiguous() or (nt > 1 and W.stride(0) < nA * nG):
+        W = W.contiguous()
+    return W, (W.stride(0) if nt > 1 else nA * nG)
+
+
+def kron_covariance_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]],
+                         max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_sweep with a weight per eigenbasis entry instead of a rank-one pair:
+    cov[t, b, c, c'] = sum_l sum_{i,g} W_l[t, i, g] Y_l[b, c][i, g] Y_l[b, c'][i, g],
+    Y_l[b, c] = VA_l^T M_l[b, c] VG_l projected once for all t.
+
+    terms: [(J_l, VA_l, VG_l, W_l)], J, VA, VG as kron_covariance_sweep takes them, W
+    (nt, nA, nG) or (nA, nG) non-negative (efb_weights).  Returns (nt, nb, nc, nc) fp32 with
+    kron_covariance_sweep's guarantees: bitwise symmetric blocks, a sample's block depends on
+    that sample only, slice t has the bits of the call with W[t] alone.  Shapes are checked
+    (ValueError) before anything touches the device.
+    """
+    if not terms:
+        raise ValueError("no terms")
+    parsed = []
+    nb = nc = nt = None
+    for J, VA, VG, W in terms:
+        nA, nG, W3 = _full_shapes(VA, VG, W)
+        J3, ld = _cov_rows(J, nA * nG)
+        if nb is None:
+            nb, nc, nt = J3.shape[0], J3.shape[1], W3.shape[0]
+        elif (J3.shape[0], J3.shape[1]) != (nb, nc):
+            raise ValueError("all terms need the same (nb, nc)")
+        if W3.shape[0] != nt or nt == 0:
+            raise ValueError("all weights need the same number nt >= 1 of matrices")
+        if nc > MAX_COV_CLASSES:
+            raise ValueError(f"kron_covariance_full handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        parsed.append((J3, ld, nA, nG, VA, VG, W3))
+    keep, jobs = [], []
+    for J3, ld, nA, nG, VA, VG, W3 in parsed:
+        VAc, ldA = _sweep_basis(VA, "VA")
+        VGc, ldG = _sweep_basis(VG, "VG")
+        N.require_device(J3, "J")
+        Wc, ldW = _full_weights(W3)
+        keep.extend([J3, VAc, VGc, Wc])
+        jobs.append((J3.data_ptr(), ld, nA, nG, VAc.data_ptr(), ldA, VGc.data_ptr(), ldG, Wc.data_ptr(), ldW))
+
+    def build(i, b0, t0):
+        j = jobs[i]
+        return N.CovFullJob(j[0] + 4 * b0 * nc * j[1], *j[1:8], j[8] + 4 * t0 * j[9], j[9])
+
+    return _run_sweep(build, N.kron_cov_full_workspace_bytes, N.kron_cov_full, len(jobs), nb, nc, nt,
+                      keep[0].device, max_workspace_bytes)
+
+
+def kron_covariance_outer_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
+                               max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_full for Linear layers without their Jacobian rows:
+    cov[t, b] = sum_l Q_l[b] diag(r_l[t, b]) Q_l[b]^T, r_l[t, b][g] = sum_i p_l[b][i]^2 W_l[t, i, g],
+    with p_l[b] = VA_l^T [a_l[b] | 1] and Q_l[b] = D_l[b] VG_l projected once for all t.
+
+    terms: [(a_l, D_l, VA_l, VG_l, W_l)], a, D, VA, VG as kron_covariance_outer_sweep takes
+    them, W (nt, nA, nG) or (nA, nG).  Returns (nt, nb, nc, nc) fp32 with
+    kron_covariance_full's guarantees.
+    """
+    if not terms:
+        raise ValueError("no terms")
+    parsed = []
+    nb = nc = nt = None
+    for a, D, VA, VG, W in terms:
+        nA, nG, W3 = _full_shapes(VA, VG, W)
+        D3, ldD = _cov_rows(D, nG)
+        a2 = a.detach()
+        a2 = a2.reshape(1, -1) if a2.dim() == 1 else a2
+        if a2.dim() != 2:
+            raise ValueError(f"a {tuple(a2.shape)}: expected (nb, cols), a Linear layer's 2-D input")
+        cols = a2.shape[1]
+        if nA not in (cols, cols + 1) or cols == 0:
+            raise ValueError(f"a has {cols} columns, VA {tuple(VA.shape)} needs {nA} or {nA - 1}")
+        if nb is None:
+            nb, nc, nt = D3.shape[0], D3.shape[1], W3.shape[0]
+        elif (D3.shape[0], D3.shape[1]) != (nb, nc):
+            raise ValueError("all terms need the same (nb, nc)")
+        if a2.shape[0] != nb:
+            raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
+        if W3.shape[0] != nt or nt == 0:
+            raise ValueError("all weights need the same number nt >= 1 of matrices")
+        if nc > MAX_COV_CLASSES:
+            raise ValueError(f"kron_covariance_outer_full handles at most {MAX_COV_CLASSES} outputs, "
+                             f"got {nc}")
+        parsed.append((a2, cols, D3, ldD, nA, nG, VA, VG, W3))
+    keep, jobs = [], []
+    for a2, cols, D3, ldD, nA, nG, VA, VG, W3 in parsed:
+        VAc, ldA = _sweep_basis(VA, "VA")
+        VGc, ldG = _sweep_basis(VG, "VG")
+        if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols):
+            a2 = a2.contiguous()
+        lda = a2.stride(0) if nb > 1 else cols
+        for t, what in ((a2, "a"), (D3, "D")):
+            N.require_device(t, what)
+        Wc, ldW = _full_weights(W3)
+        keep.extend([a2, D3, VAc, VGc, Wc])
+        jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0,
+                     VAc.data_ptr(), ldA, VGc.data_ptr(), ldG, Wc.data_ptr(), ldW))
+
+    def build(i, b0, t0):
+        j = jobs[i]
+        return N.CovOuterFullJob(j[0] + 4 * b0 * j[1], j[1], j[2], j[3], j[4] + 4 * b0 * nc * j[5],
+                                 *j[5:12], j[12] + 4 * t0 * j[13], j[13])
+
+    return _run_sweep(build, N.kron_cov_outer_full_workspace_bytes, N.kron_cov_outer_full, len(jobs),
+                      nb, nc, nt, keep[0].device, max_workspace_bytes)
+
+
+def efb_weights(lam: Tensor, dampings: Sequence[Tuple[float, float]]) -> Tensor:
+    """W[t, i, g] = 1 / (s_t lam[g, i] + n_t) for dampings [(add n_t, multiply s_t)] and an EFB
+    state entry lam (nG, nA): (nt, nA, nG) fp32, the TRANSPOSE of the state's layout (the
+    posterior's order), EFB.invert's inv_state squared; EFB damps with s and n themselves, not
+    their square roots.  Computed in fp64 on lam's device.  Raises numpy.linalg.LinAlgError
+    if any s lam + n is not positive.  Pure torch."""
+    if lam.dim() != 2:
+        raise ValueError(f"lam {tuple(lam.shape)}: expected an EFB state entry (nG, nA)")
+    d = torch.tensor([[float(n), float(s)] for n, s in dampings], dtype=torch.float64,
+                     device=lam.device).reshape(-1, 2)
+    r = d[:, 1].reshape(-1, 1, 1) * lam.detach().to(torch.float64).t().unsqueeze(0) + d[:, 0].reshape(-1, 1, 1)
+    if not bool((r > 0).all()):
+        raise np.linalg.LinAlgError("efb_weights: multiply * eigenvalue + add is not positive")
+    return r.reciprocal().to(torch.float32).contiguous()
+
+
+def _efb_layers(efb, layers):
+    if layers is None:
+        layers = [m for m in list(efb.model.modules())[1:] if m in efb.state]
+    return list(layers)
+
+
+def _efb_chunk(model, layers, basis, x, jacobians):
+    """(logits, cov (nt, n, nc, nc)) of one chunk; basis[layer] = (VA, VG, W (nt, nA, nG))."""
+    if jacobians == "dense":
+        f, Js = output_jacobians(model, layers, x)
+        return f, kron_covariance_full([(J, *basis[layer]) for layer, J in zip(layers, Js)])
+    f, io = layer_io_jacobians(model, layers, x)
+    outer, dense = [], []
+    for layer, (a, D) in zip(layers, io):
+        if isinstance(layer, torch.nn.Linear):
+            if a.dim() != 2:
+                raise ValueError(f"the factored route needs 2-D Linear inputs, got {tuple(a.shape)}")
+            outer.append((a, D, *basis[layer]))
+        elif isinstance(layer, torch.nn.Conv2d):
+            dense.append((_conv_rows(layer, a, D), *basis[layer]))
+        else:
+            raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
+                             f"{layer.__class__.__name__}")
+    cov = kron_covariance_outer_full(outer) if outer else None
+    if dense:
+        conv = kron_covariance_full(dense)
+        cov = conv if cov is None else cov + conv
+    return f, cov
+
+
+def glm_predictive_efb(efb, x: Tensor, layers: Iterable = None, chunk: int = 64, jacobians: str = "dense"):
+    """glm_predictive under the EFB posterior (EFB.invert's inv_state, the Gaussian EFB.sample
+    draws from): (logits (N, nc), cov (N, nc, nc)) with
+    cov = sum_l sum_{i,g} W_l[i][g] Y_l[i][g] Y_l'[i][g], Y = V_A^T M V_G, W = inv_state^T squared,
+    in chunks of `chunk` samples: no sampling loop, no weight replacement.  `jacobians` as in
+    glm_predictive: "dense" sends output_jacobians' rows through kron_covariance_full;
+    "factored" sends Linear layers through kron_covariance_outer_full and Conv2d layers through
+    kron_covariance_full on rows formed from the same captures."""
+    if jacobians not in ("dense", "factored"):
+        raise ValueError(f"jacobians must be 'dense' or 'factored', got {jacobians!r}")
+    assert efb.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
+    layers = _efb_layers(efb, layers)
+    basis = {layer: (*efb.eigvecs[layer], (efb.inv_state[layer].detach().t() ** 2).contiguous().unsqueeze(0))
+             for layer in layers}
+    logits, covs = [], []
+    for c0 in range(0, x.shape[0], chunk):
+        f, cov = _efb_chunk(efb.model, layers, basis, x[c0:c0 + chunk], jacobians)
+        logits.append(f)
+        covs.append(cov[0])
+    return torch.cat(logits), torch.cat(covs)
+
+
+def glm_predictive_efb_sweep(efb, x: Tensor, dampings, layers: Iterable = None, chunk: int = 64,
+                             jacobians: str = "dense", max_weight_bytes: int = 1 << 30) -> Tensor:
+    """glm_predictive_efb's covariance for a grid of dampings straight from `efb.state`:
+    cov (nt, N, nc, nc), cov[t] what `efb.invert(*dampings[t])` followed by glm_predictive_efb
+    gives.  No invert call is needed (EFB.invert is elementwise: a grid point is a weight
+    matrix, efb_weights).  `dampings`: a sequence of (add, multiply), each a scalar pair or two
+    per-layer lists.  The weights are built for as many grid points at a time as fit in
+    `max_weight_bytes` over all layers (a 4097 x 4096 layer's matrix is 67 MB per grid point);
+    within such a group the forward pass, the Jacobians or captures and the projections are
+    shared."""
+    if jacobians not in ("dense", "factored"):
+        raise ValueError(f"jacobians must be 'dense' or 'factored', got {jacobians!r}")
+    assert efb.state, "State dict is empty. Did you call 'update' prior to this?"
+    entries = list(efb.state)
+    layers = _efb_layers(efb, layers)
+    grid = _damping_grid(dampings, len(entries))
+    per_point = sum(4 * efb.state[layer].numel() for layer in layers)
+    group = max(1, min(len(grid), max_weight_bytes // max(per_point, 1)))
+    out = []
+    for t0 in range(0, len(grid), group):
+        points = grid[t0:t0 + group]
+        basis = {layer: (*efb.eigvecs[layer],
+                         efb_weights(efb.state[layer], [p[entries.index(layer)] for p in points]))
+                 for layer in layers}
+        covs = [_efb_chunk(efb.model, layers, basis, x[c0:c0 + chunk], jacobians)[1]
+                for c0 in range(0, x.shape[0], chunk)]
+        out.append(torch.cat(covs, dim=1))
+        del basis
+    return torch.cat(out)
+
+
+def efb_log_det_sweep(efb, dampings) -> Tensor:
+    """log det of the damped EFB curvature per grid point: out[t] = sum_layers sum log(s lam + n)
+    over every entry of `efb.state`, the other half of an evidence-style criterion (as
+    log_det_sweep is for KFAC).  Returns (nt,) fp64.  Raises numpy.linalg.LinAlgError if any
+    s lam + n is not positive.  Pure torch."""
+    assert efb.state, "State dict is empty. Did you call 'update' prior to this?"
+    entries = list(efb.state.values())
+    grid = _damping_grid(dampings, len(entries))
+    out = torch.zeros(len(grid), dtype=torch.float64, device=entries[0].device)
+    for index, lam in enumerate(entries):
+        d = torch.tensor([[float(point[index][0]), float(point[index][1])] for point in grid],
+                         dtype=torch.float64, device=lam.device)
+        r = d[:, 1:2] * lam.detach().to(torch.float64).reshape(1, -1) + d[:, 0:1]
+        if not bool((r > 0).all()):
+            raise np.linalg.LinAlgError("efb_log_det_sweep: multiply * eigenvalue + add is not positive")
+        out += r.log().sum(dim=1)
+    return out
+
+
 def probit_predictive(logits: Tensor, cov: Tensor) -> Tensor:
     """softmax(logits / sqrt(1 + pi/8 * diag(cov))): the probit approximation of
     E[softmax(f)] for f ~ N(logits, cov).  Pure torch."""

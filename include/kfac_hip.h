@@ -417,6 +417,64 @@ KFAC_API int kfac_kron_cov_outer_sweep(const kfac_cov_outer_sweep_job* jobs, int
                                        int nc, int nt, int accumulate, float* cov, void* workspace,
                                        size_t workspace_bytes, kfac_stream_t stream);
 
+/* ------------------- GLM predictive covariance with per-entry eigenbasis weights
+ * The sweep calls' weights are rank one, w[i][g] = wA[i] wG[g]; a posterior that keeps the
+ * KFAC eigenbases but refits every one of the nA*nG eigenvalues (EFB.sample draws
+ * S = VA (Z o Lambda^-T) VG^T, Lambda^- = EFB.inv_state (nG x nA)) needs an arbitrary
+ * non-negative W[i][g] (for EFB: W[i][g] = Lambda^-[g][i]^2).  For nt weight matrices at
+ * once (1 <= nt <= 64), cov is nt x nb x nc x nc:
+ *   kfac_kron_cov_full        Y_{b,c} = VA^T M_{b,c} VG once per call, then
+ *     cov[t][b][c][c'] (+)= sum_j sum_{i,g} W_t[i][g] Y_{b,c}[i][g] Y_{b,c'}[i][g]
+ *   kfac_kron_cov_outer_full  p_b = VA^T abar_b and Q_b = Delta_b VG once per call, then
+ *     cov[t][b] (+)= sum_j Q_b diag(r_{t,b}) Q_b^T ,  r_{t,b}[g] = sum_i p_b[i]^2 W_t[i][g]
+ *     (r = (P o P) W_t: one nb x nA by nA x nG GEMM per grid point)
+ * W is nt matrices in the posterior's flat order i*nG + g, grid point t at W + t*ldW,
+ * ldW >= nA*nG.  The weights are plain non-negative numbers: the calls know nothing of
+ * damping.  Guarantees (the sweep calls'): every reduction runs in a fixed order, the sums
+ * across segments and across jobs in fp64; no atomics; two calls give identical bits; every
+ * nc x nc block is bitwise symmetric with a non-negative diagonal; a sample's block depends
+ * on that sample only; slice t of an nt-call has the bits of the nt = 1 call with W_t.
+ * At most 8 jobs and nc <= 32 per call; KFAC_EINVAL is returned before any launch,
+ * KFAC_EWORKSPACE when the workspace is smaller than the query's answer.                */
+typedef struct kfac_cov_full_job {
+  const float* J; /* as kfac_cov_job */
+  int64_t ldJ;
+  int32_t nA, nG;
+  const float* VA; /* nA x nA, eigenvectors as columns */
+  int64_t ldA;
+  const float* VG; /* nG x nG */
+  int64_t ldG;
+  const float* W; /* nt x (nA*nG), element (t, i, g) at W[t*ldW + i*nG + g] */
+  int64_t ldW;
+} kfac_cov_full_job;
+
+KFAC_API size_t kfac_kron_cov_full_workspace_bytes(const kfac_cov_full_job* jobs, int njobs, int64_t nb,
+                                                   int nc, int nt);
+KFAC_API int kfac_kron_cov_full(const kfac_cov_full_job* jobs, int njobs, int64_t nb, int nc, int nt,
+                                int accumulate, float* cov, void* workspace, size_t workspace_bytes,
+                                kfac_stream_t stream);
+
+typedef struct kfac_cov_outer_full_job {
+  const float* a; /* as kfac_cov_outer_job */
+  int64_t lda;
+  int32_t cols, has_ones;
+  const float* D;
+  int64_t ldD;
+  int32_t nG, reserved;
+  const float* VA; /* nA x nA, nA = cols + has_ones */
+  int64_t ldA;
+  const float* VG; /* nG x nG */
+  int64_t ldG;
+  const float* W; /* nt x (nA*nG), as kfac_cov_full_job */
+  int64_t ldW;
+} kfac_cov_outer_full_job;
+
+KFAC_API size_t kfac_kron_cov_outer_full_workspace_bytes(const kfac_cov_outer_full_job* jobs, int njobs,
+                                                         int64_t nb, int nc, int nt);
+KFAC_API int kfac_kron_cov_outer_full(const kfac_cov_outer_full_job* jobs, int njobs, int64_t nb, int nc,
+                                      int nt, int accumulate, float* cov, void* workspace,
+                                      size_t workspace_bytes, kfac_stream_t stream);
+
 /* -------------------------------------------------------- posterior samples
  * out_j = (LA_j Z_j LG_j^T)^T, shape (nG x nA): KFAC.sample, curvatures.py:400-405,
  * with Z (nA x nG row-major) supplied by the caller (torch.randn, the reference's
