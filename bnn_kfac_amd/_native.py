@@ -137,6 +137,7 @@ SIGNATURES = {
                                           ctypes.c_size_t, c_vp]),
     "kfac_factor_accum_plan": (ctypes.c_int, [ctypes.POINTER(FactorJob), ctypes.c_int,
                                               ctypes.POINTER(c_i32), ctypes.POINTER(ctypes.c_size_t)]),
+    "kfac_factor_route": (ctypes.c_int, [ctypes.POINTER(FactorJob), ctypes.c_int, ctypes.POINTER(c_i32)]),
     "kfac_factor_flush": (ctypes.c_int, [ctypes.POINTER(FactorJob), ctypes.c_int, c_vp]),
     "kfac_x3_unit_table": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_i32), ctypes.c_int]),
     "kfac_syrk_linear": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, ctypes.c_int, c_f32, c_f32,
@@ -413,6 +414,14 @@ def factor_accum_plan(jobs):
     nbytes = (ctypes.c_size_t * len(jobs))()
     check(lib().kfac_factor_accum_plan(arr, len(jobs), splits, nbytes), "kfac_factor_accum_plan")
     return list(zip(splits, nbytes))
+
+
+def factor_route(jobs):
+    """[kfac_prof_id] of the kernel family each job's launch group is first routed to
+    (kfac_factor_route: host only, no device call)."""
+    family = (c_i32 * len(jobs))()
+    check(lib().kfac_factor_route(as_array(FactorJob, jobs), len(jobs), family), "kfac_factor_route")
+    return list(family)
 
 
 def factor_flush(jobs, device: torch.device, stream: int = None):

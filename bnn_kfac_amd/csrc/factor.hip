@@ -529,6 +529,19 @@ extern "C" int kfac_factor_accum_plan(const kfac_factor_job* jobs, int njobs, in
   return KFAC_OK;
 }
 
+extern "C" int kfac_factor_route(const kfac_factor_job* jobs, int njobs, int32_t* family) {
+  if (validate(jobs, njobs) != KFAC_OK || (njobs > 0 && !family)) return KFAC_EINVAL;
+  std::vector<kfac_factor_job> sorted;
+  std::vector<int> order;
+  std::vector<std::pair<int, int>> groups;
+  launch_groups(jobs, njobs, sorted, order, groups);
+  for (const auto& g : groups) {
+    const int fam = route_group(sorted.data() + g.first, g.second).family;
+    for (int k = 0; k < g.second; ++k) family[order[g.first + k]] = fam;
+  }
+  return KFAC_OK;
+}
+
 // One launch group of kfac_factor_update: routed here, and routed again for every group
 // this function rewrites.  A ragged multi-batch job (x.last_rows) runs in one launch on
 // kfac_factor_tiles_x3 (and its narrow tasks); any other kernel, or a group past the

@@ -125,6 +125,16 @@ KFAC_API int kfac_factor_update(const kfac_factor_job* jobs, int njobs, void* wo
  * batches of any row count may use it).                                    */
 KFAC_API int kfac_factor_accum_plan(const kfac_factor_job* jobs, int njobs, int32_t* splits,
                            size_t* bytes);
+/* Which kernel family these jobs would run on, for inspection; no GPU needed and no
+ * device call made.  family[j] = the kfac_prof_id (below) of the family job j's launch
+ * group gets from the grouping and the router kfac_factor_update uses (row-major jobs
+ * share groups of up to 16, every conv job is a group of its own), after
+ * kfac_factor_accum_plan's validation (KFAC_EINVAL; a NULL `family` too).  It reports
+ * the FIRST routing of the group: a multi-batch conv job off the image-staged kernels
+ * answers KFAC_PROF_FACTOR_TILES and runs there, one launch per batch; a group
+ * kfac_factor_update splits (a ragged last batch, more than 64 batch bases) is routed
+ * again per piece.                                                            */
+KFAC_API int kfac_factor_route(const kfac_factor_job* jobs, int njobs, int32_t* family);
 /* F = beta*F + alpha*sum(acc) for every job (all must carry acc): the reduce
  * step of kfac_factor_update, deferred (x is only read for the factor size). */
 KFAC_API int kfac_factor_flush(const kfac_factor_job* jobs, int njobs, kfac_stream_t stream);

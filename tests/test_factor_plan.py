@@ -133,6 +133,26 @@ EXPECTED = {
 }
 
 
+# the kernel family (kfac_prof_id) each job's launch group is first routed to
+# (kfac_factor_route): 0 tiles, 4 syrk3, 5 tiles_x3, 6 conv, 7 channel_small, 9 conv_x3,
+# 10 conv_x3s, 11 conv_x3f, 12 channel_x3
+ROUTES = {
+    "c2": [0, 0, 0, 0],
+    "c5": [4, 4, 4, 4, 4, 4],
+    "lenet_all": [10, 7, 11, 12, 5, 5],
+    "conv_x3_51": [9],
+    "conv_fp32_n10": [6],
+    "conv_fp32_n224": [6],
+    "conv_x3s_odd_groups": [6],
+    "conv_col_stride3": [6],
+    "conv_image_too_large": [0],
+    "channel_L_not_x4": [0],
+    "channel_with_ones": [0],
+    "channel_multibatch": [7],
+    "channel_multibatch_misaligned": [0],
+}
+
+
 def measure(N, name):
     built = CASES[name](N)  # (the keepalives hold the host base tables until the calls return)
     jobs = [b[0] for b in built]
@@ -148,3 +168,10 @@ def test_plan_and_workspace_unchanged(name):
     splits, nbytes, ws = measure(N, name)
     print(name, splits, nbytes, ws)
     assert (splits, nbytes, ws) == EXPECTED[name]
+
+
+@pytest.mark.parametrize("name", list(ROUTES))
+def test_route_unchanged(name):
+    from bnn_kfac_amd import _native as N
+    built = CASES[name](N)
+    assert N.factor_route([b[0] for b in built]) == ROUTES[name]
