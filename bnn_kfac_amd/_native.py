@@ -180,6 +180,15 @@ SIGNATURES = {
     "kfac_kron_cov_outer_joint": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64,
                                                  ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_vp,
                                                  ctypes.c_size_t, c_vp]),
+    "kfac_kron_cov_tiled_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64,
+                                                              ctypes.c_int]),
+    "kfac_kron_cov_tiled": (ctypes.c_int, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                           ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_kron_cov_outer_tiled_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovOuterJob),
+                                                                    ctypes.c_int, c_i64, ctypes.c_int]),
+    "kfac_kron_cov_outer_tiled": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64,
+                                                 ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_size_t,
+                                                 c_vp]),
     "kfac_kron_cov_sweep_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovSweepJob), ctypes.c_int,
                                                               c_i64, ctypes.c_int, ctypes.c_int]),
     "kfac_kron_cov_sweep": (ctypes.c_int, [ctypes.POINTER(CovSweepJob), ctypes.c_int, c_i64, ctypes.c_int,
@@ -607,6 +616,46 @@ def kron_cov_outer_joint(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: 
     check(L.kfac_kron_cov_outer_joint(arr, len(jobs), nb, nc, int(accumulate), ptr(out), out.stride(0),
                                       ptr(ws), ws.numel(), stream_handle(out.device)),
           "kfac_kron_cov_outer_joint")
+
+
+def _blocks_out(out: torch.Tensor, nb: int, nc: int, what: str):
+    """The tiled calls write nb contiguous nc x nc blocks: refuse anything else."""
+    if tuple(out.shape) != (nb, nc, nc) or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous ({nb}, {nc}, {nc}) tensor, got "
+                         f"{tuple(out.shape)} / {out.stride()}")
+    require_device(out, what)
+
+
+def kron_cov_tiled_workspace_bytes(jobs, nb: int, nc: int) -> int:
+    return lib().kfac_kron_cov_tiled_workspace_bytes(as_array(CovJob, jobs), len(jobs), nb, nc)
+
+
+def kron_cov_tiled(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_kron_cov_tiled: out (nb, nc, nc) (+)= sum_j T_j T_j^T per sample, any nc, <= 8 jobs
+    per call."""
+    _blocks_out(out, nb, nc, "kron_cov_tiled")
+    L = lib()
+    arr = as_array(CovJob, jobs)
+    need = L.kfac_kron_cov_tiled_workspace_bytes(arr, len(jobs), nb, nc)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_kron_cov_tiled(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
+                                stream_handle(out.device)), "kfac_kron_cov_tiled")
+
+
+def kron_cov_outer_tiled_workspace_bytes(jobs, nb: int, nc: int) -> int:
+    return lib().kfac_kron_cov_outer_tiled_workspace_bytes(as_array(CovOuterJob, jobs), len(jobs), nb, nc)
+
+
+def kron_cov_outer_tiled(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_kron_cov_outer_tiled: out (nb, nc, nc) (+)= sum_j s_j V_j V_j^T per sample, any nc,
+    <= 8 jobs per call."""
+    _blocks_out(out, nb, nc, "kron_cov_outer_tiled")
+    L = lib()
+    arr = as_array(CovOuterJob, jobs)
+    need = L.kfac_kron_cov_outer_tiled_workspace_bytes(arr, len(jobs), nb, nc)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_kron_cov_outer_tiled(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws),
+                                      ws.numel(), stream_handle(out.device)), "kfac_kron_cov_outer_tiled")
 
 
 def kron_cov_sweep_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:

@@ -4,7 +4,8 @@
 // nc x nc Gram block -- and what their damping sweeps share: the weight views and the
 // weighted Gram of a staged segment for a group of grid points; and what the joint calls
 // (covariance_joint.hip) take from both: the argument blocks of the apply / V launches, the
-// Abar^T panel, and the 64x64 Gram tile all three of their operands go through.
+// Abar^T panel, and the 64x64 Gram tile all three of their operands go through; the
+// class-tiled per-sample calls (covariance_tiled.hip) run that tile on one sample's rows.
 #pragma once
 
 #include "kfac_common.h"
@@ -238,6 +239,8 @@ static_assert(sizeof(OuterArgs) <= 4096, "kernel argument block");
 // all rows of every job; kfac_cov_outer_v (covariance_outer.hip): V = Delta K2.
 int cov_launch_apply(const CovArgs& args, hipStream_t s);
 int cov_launch_outer_v(const OuterArgs& args, int64_t nv, hipStream_t s);
+// kfac_cov_rownorm (covariance_outer.hip) on a filled block: norm[tile][b], nn tasks.
+int cov_launch_rownorm(const OuterArgs& args, int64_t nn, hipStream_t s);
 // kfac_cov_sweep_reduce (covariance.hip) on a block whose njobs, nc, nb, accumulate, cov and
 // the jobs' partial (ntau x nb x nseg x nc*nc) / nseg are filled.
 int cov_launch_sweep_reduce(const CovArgs& args, int ntau, hipStream_t s);
@@ -293,6 +296,9 @@ static inline bool cov_job_ok(const kfac_cov_job& q) {
 static inline int64_t outer_nA(const kfac_cov_outer_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
 static inline size_t outer_v_bytes(const kfac_cov_outer_job& j, int64_t rows) {
   return align_up((size_t)rows * (size_t)j.nG * sizeof(float), 256);
+}
+static inline size_t outer_norm_bytes(const kfac_cov_outer_job& j, int64_t nb) {
+  return align_up((size_t)(cdiv(outer_nA(j), TILE) * nb) * sizeof(float), 256);
 }
 static inline bool outer_job_ok(const kfac_cov_outer_job& q) {
   return q.a && q.D && q.K1 && q.K2 && q.cols > 0 && q.nG > 0 && q.lda >= q.cols &&
@@ -359,7 +365,8 @@ static inline bool cov_fill_outer(const kfac_cov_outer_job* jobs, int njobs, int
   return true;
 }
 
-// ---- joint covariance (kfac_kron_cov_joint / kfac_kron_cov_outer_joint)
+// ---- joint covariance (kfac_kron_cov_joint / kfac_kron_cov_outer_joint) and the class-tiled
+// per-sample covariance (kfac_kron_cov_tiled / kfac_kron_cov_outer_tiled)
 constexpr int JSEG = GSEG;          // K elements per joint-gram task: a function of K alone
 constexpr int JTILE2 = TILE * TILE; // floats per tile partial
 

@@ -224,6 +224,13 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_sweep_reduce(OuterArg
   }
 }
 
+// The row-norm launch alone (kfac_kron_cov_outer_tiled forms its own Grams from V).
+int cov_launch_rownorm(const OuterArgs& args, int64_t nn, hipStream_t s) {
+  hipLaunchKernelGGL(kfac_cov_rownorm, dim3((unsigned)nn), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}
+
 // The V launch alone (kfac_kron_cov_outer_joint forms its own Grams from U and V).
 int cov_launch_outer_v(const OuterArgs& args, int64_t nv, hipStream_t s) {
   hipLaunchKernelGGL(kfac_cov_outer_v, dim3((unsigned)nv), dim3(NTHREADS), 0, s, args);
@@ -232,9 +239,6 @@ int cov_launch_outer_v(const OuterArgs& args, int64_t nv, hipStream_t s) {
 }
 
 static int64_t outer_nseg(const kfac_cov_outer_job& j) { return cdiv(j.nG, GSEG); }
-static size_t outer_norm_bytes(const kfac_cov_outer_job& j, int64_t nb) {
-  return align_up((size_t)(cdiv(outer_nA(j), TILE) * nb) * sizeof(float), 256);
-}
 static size_t outer_partial_bytes(const kfac_cov_outer_job& j, int64_t nb, int nc) {
   return align_up((size_t)(nb * outer_nseg(j)) * nc * nc * sizeof(float), 256);
 }

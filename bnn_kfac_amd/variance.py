@@ -9,7 +9,8 @@ the reference builds them (sampling_free/utils.py:221-226).
 
 The GLM predictive (glm_predictive / probit_predictive, further down) goes beyond the
 reference: logits and their full covariance under the KFAC posterior in closed form
-(`kfac_kron_cov`), where the reference samples weights and re-runs the network.
+(`kfac_kron_cov`; above 32 outputs `kfac_kron_cov_tiled`), where the reference samples weights
+and re-runs the network.
 """
 from __future__ import annotations
 
@@ -263,6 +264,36 @@ def _cov_jobs(terms, lower: bool, who: str, max_classes: int = None):
     return keep, jobs, nb, nc
 
 
+def _cov_job_at(j, b0: int, nc: int):
+    """The kfac_cov_job tuple j with its rows starting at sample b0."""
+    return (j[0] + 4 * b0 * nc * j[1], *j[1:])
+
+
+def _run_per_sample(jobs, struct, job_at, workspace_bytes, call, nb, nc, device, max_workspace_bytes):
+    """What the per-sample calls share: the (nb, nc, nc) result, jobs folded in groups of 8
+    with `accumulate`, the samples cut into chunks that need at most `max_workspace_bytes` of
+    scratch each (`job_at(j, b0, nc)`: job tuple j moved to sample b0)."""
+    out = torch.empty(nb, nc, nc, dtype=torch.float32, device=device)
+    if nb == 0:
+        return out
+    groups = [jobs[i:i + 8] for i in range(0, len(jobs), 8)]
+
+    def need(n):
+        return max(workspace_bytes([struct(*j) for j in g], n, nc) for g in groups)
+
+    step = nb
+    while step > 1 and need(step) > max_workspace_bytes:
+        step = max(1, min(step - 1, step * max_workspace_bytes // need(step)))
+    if need(step) > max_workspace_bytes:
+        raise ValueError(f"one sample needs {need(1)} workspace bytes, max_workspace_bytes is "
+                         f"{max_workspace_bytes}")
+    for b0 in range(0, nb, step):
+        n = min(step, nb - b0)
+        for gi, g in enumerate(groups):
+            call([struct(*job_at(j, b0, nc)) for j in g], n, nc, out[b0:b0 + n], accumulate=gi > 0)
+    return out
+
+
 def kron_covariance(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool = True,
                     max_workspace_bytes: int = 1 << 30) -> Tensor:
     """cov[b, c, c'] = sum_l J_l[b, c] (K1_l K1_l^T kron K2_l K2_l^T) J_l[b, c']^T.
@@ -275,26 +306,25 @@ def kron_covariance(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool 
     on that sample only, so chunking does not change a bit).
     """
     keep, jobs, nb, nc = _cov_jobs(terms, lower, "kron_covariance", MAX_COV_CLASSES)
-    out = torch.empty(nb, nc, nc, dtype=torch.float32, device=keep[0].device)
-    if nb == 0:
-        return out
-    groups = [jobs[i:i + 8] for i in range(0, len(jobs), 8)]
+    return _run_per_sample(jobs, N.CovJob, _cov_job_at, N.kron_cov_workspace_bytes, N.kron_cov, nb, nc,
+                           keep[0].device, max_workspace_bytes)
 
-    def need(n):
-        return max(N.kron_cov_workspace_bytes([N.CovJob(*j) for j in g], n, nc) for g in groups)
 
-    step = nb
-    while step > 1 and need(step) > max_workspace_bytes:
-        step = max(1, min(step - 1, step * max_workspace_bytes // need(step)))
-    if need(step) > max_workspace_bytes:
-        raise ValueError(f"one sample needs {need(1)} workspace bytes, max_workspace_bytes is "
-                         f"{max_workspace_bytes}")
-    for b0 in range(0, nb, step):
-        n = min(step, nb - b0)
-        for gi, g in enumerate(groups):
-            arr = [N.CovJob(j[0] + 4 * b0 * nc * j[1], *j[1:]) for j in g]
-            N.kron_cov(arr, n, nc, out[b0:b0 + n], accumulate=gi > 0)
-    return out
+def kron_covariance_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool = True,
+                          max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance for any number of outputs (a CIFAR-100 or ImageNet head): the same
+    terms, the same (nb, nc, nc) fp32 result, nc not capped (kfac_kron_cov_tiled: a sample's
+    block in 64x64 class tiles).
+
+    Every block is bitwise symmetric, two calls give identical bits, terms fold in groups of
+    8 and the samples are chunked under `max_workspace_bytes` without changing a bit, as in
+    kron_covariance.  Block b has exactly the bits of kron_covariance_joint's block
+    cov[b, :, b, :] on the same terms (marginal_blocks); against kron_covariance (nc <= 32,
+    another summation order) it agrees to fp32 rounding.
+    """
+    keep, jobs, nb, nc = _cov_jobs(terms, lower, "kron_covariance_tiled")
+    return _run_per_sample(jobs, N.CovJob, _cov_job_at, N.kron_cov_tiled_workspace_bytes,
+                           N.kron_cov_tiled, nb, nc, keep[0].device, max_workspace_bytes)
 
 
 def output_jacobians(model: torch.nn.Module, layers: Sequence[torch.nn.Module], x: Tensor):
@@ -492,6 +522,11 @@ def _cov_outer_jobs(terms, lower: bool, who: str, max_classes: int = None):
     return keep, jobs, nb, nc
 
 
+def _cov_outer_job_at(j, b0: int, nc: int):
+    """The kfac_cov_outer_job tuple j with a and D starting at sample b0."""
+    return (j[0] + 4 * b0 * j[1], j[1], j[2], j[3], j[4] + 4 * b0 * nc * j[5], *j[5:])
+
+
 def kron_covariance_outer(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]], lower: bool = True,
                           max_workspace_bytes: int = 1 << 30) -> Tensor:
     """kron_covariance for Linear layers without their Jacobian rows:
@@ -506,33 +541,39 @@ def kron_covariance_outer(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]]
     so chunking does not change a bit).
     """
     keep, jobs, nb, nc = _cov_outer_jobs(terms, lower, "kron_covariance_outer", MAX_COV_CLASSES)
-    out = torch.empty(nb, nc, nc, dtype=torch.float32, device=keep[0].device)
-    if nb == 0:
-        return out
-    groups = [jobs[i:i + 8] for i in range(0, len(jobs), 8)]
+    return _run_per_sample(jobs, N.CovOuterJob, _cov_outer_job_at, N.kron_cov_outer_workspace_bytes,
+                           N.kron_cov_outer, nb, nc, keep[0].device, max_workspace_bytes)
 
-    def need(n):
-        return max(N.kron_cov_outer_workspace_bytes([N.CovOuterJob(*j) for j in g], n, nc) for g in groups)
 
-    step = nb
-    while step > 1 and need(step) > max_workspace_bytes:
-        step = max(1, min(step - 1, step * max_workspace_bytes // need(step)))
-    if need(step) > max_workspace_bytes:
-        raise ValueError(f"one sample needs {need(1)} workspace bytes, max_workspace_bytes is "
-                         f"{max_workspace_bytes}")
-    for b0 in range(0, nb, step):
-        n = min(step, nb - b0)
-        for gi, g in enumerate(groups):
-            arr = [N.CovOuterJob(j[0] + 4 * b0 * j[1], j[1], j[2], j[3], j[4] + 4 * b0 * nc * j[5], *j[5:])
-                   for j in g]
-            N.kron_cov_outer(arr, n, nc, out[b0:b0 + n], accumulate=gi > 0)
-    return out
+def kron_covariance_outer_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]], lower: bool = True,
+                                max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_outer for any number of outputs: the same terms, the same (nb, nc, nc)
+    fp32 result, nc not capped (kfac_kron_cov_outer_tiled).  A 512 -> 1000 head costs its
+    V = D K2 (nb*1000 x 1000) and the Gram partials, never a Jacobian row.
+
+    Every block is bitwise symmetric, two calls give identical bits, terms fold in groups of
+    8 and the samples are chunked under `max_workspace_bytes` without changing a bit, as in
+    kron_covariance_outer; against it (nc <= 32, another summation order) the result agrees
+    to fp32 rounding.
+    """
+    keep, jobs, nb, nc = _cov_outer_jobs(terms, lower, "kron_covariance_outer_tiled")
+    return _run_per_sample(jobs, N.CovOuterJob, _cov_outer_job_at, N.kron_cov_outer_tiled_workspace_bytes,
+                           N.kron_cov_outer_tiled, nb, nc, keep[0].device, max_workspace_bytes)
+
+
+def _per_sample_calls(nc: int):
+    """(dense, outer) per-sample covariance calls for nc outputs: the 32x32-quadrant kernels
+    up to MAX_COV_CLASSES, the class-tiled ones above."""
+    if nc > MAX_COV_CLASSES:
+        return kron_covariance_tiled, kron_covariance_outer_tiled
+    return kron_covariance, kron_covariance_outer
 
 
 def _glm_chunk_factored(model, layers, inv, x):
     """One chunk of the factored route: Linear layers by kron_covariance_outer, Conv2d
     layers by kron_covariance on rows formed from the same captures (_conv_rows: on the
-    device for every layer kfac_cov_conv_rows covers); the two are added."""
+    device for every layer kfac_cov_conv_rows covers); the two are added.  More than
+    MAX_COV_CLASSES outputs go through the class-tiled calls (_per_sample_calls)."""
     f, io = layer_io_jacobians(model, layers, x)
     outer, dense = [], []
     for layer, (a, D) in zip(layers, io):
@@ -545,9 +586,10 @@ def _glm_chunk_factored(model, layers, inv, x):
         else:
             raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
                              f"{layer.__class__.__name__}")
-    cov = kron_covariance_outer(outer, lower=True) if outer else None
+    cov_dense, cov_outer = _per_sample_calls(f.shape[1])
+    cov = cov_outer(outer, lower=True) if outer else None
     if dense:
-        conv = kron_covariance(dense, lower=True)
+        conv = cov_dense(dense, lower=True)
         cov = conv if cov is None else cov + conv
     return f, cov
 
@@ -576,8 +618,9 @@ def kron_covariance_joint(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower:
     sum_l J_l[b, c] (K1_l K1_l^T kron K2_l K2_l^T) J_l[b', c']^T, the joint (function-space)
     covariance of all nb*nc outputs of the call.
 
-    terms as kron_covariance takes them; nc has no cap here (nb = 1 gives one sample's full
-    covariance for any number of outputs).  Returns (nb, nc, nb, nc) fp32, a view of the
+    terms as kron_covariance takes them; nc has no cap here (for the per-sample blocks alone
+    at any number of outputs use kron_covariance_tiled, which computes no cross block and
+    has these diagonal blocks' bits).  Returns (nb, nc, nb, nc) fp32, a view of the
     contiguous (nb*nc x nb*nc) matrix, bitwise symmetric: cov[b, c, b', c'] == cov[b', c', b, c];
     its diagonal blocks cov[b, :, b, :] are kron_covariance's (marginal_blocks).  An entry
     depends on its two rows only, so the result for a subset of the samples has the bits of
@@ -652,7 +695,10 @@ def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64, ja
     (KFAC.invert's factors, the Gaussian KFAC.sample draws from): (logits (N, nc),
     cov (N, nc, nc)) with cov = sum_l J_l (L_A L_A^T kron L_G L_G^T) J_l^T, in chunks
     of `chunk` samples.  No sampling loop, no weight replacement; a regression net
-    with one output has its predictive variance in cov[:, 0, 0].
+    with one output has its predictive variance in cov[:, 0, 0].  Any number of outputs:
+    up to MAX_COV_CLASSES = 32 a chunk goes through kron_covariance / kron_covariance_outer,
+    above (a CIFAR-100 or ImageNet head) through kron_covariance_tiled /
+    kron_covariance_outer_tiled, on either route.
 
     jacobians="dense" materialises every Jacobian row (output_jacobians); "factored"
     takes one layer_io_jacobians call per chunk and never forms a Linear layer's rows
@@ -682,7 +728,8 @@ def glm_predictive(kfac, x: Tensor, layers: Iterable = None, chunk: int = 64, ja
             continue
         f, Js = output_jacobians(model, layers, x[c0:c0 + chunk])
         logits.append(f)
-        covs.append(kron_covariance([(J, *inv[layer]) for layer, J in zip(layers, Js)], lower=True))
+        cov_dense, _ = _per_sample_calls(f.shape[1])
+        covs.append(cov_dense([(J, *inv[layer]) for layer, J in zip(layers, Js)], lower=True))
     return torch.cat(logits), torch.cat(covs)
 
 

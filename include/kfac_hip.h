@@ -370,6 +370,38 @@ KFAC_API int kfac_kron_cov_outer_joint(const kfac_cov_outer_job* jobs, int njobs
                                        int accumulate, float* cov, int64_t ldc, void* workspace,
                                        size_t workspace_bytes, kfac_stream_t stream);
 
+/* ----------------------------- GLM predictive covariance, any number of outputs
+ * kfac_kron_cov / kfac_kron_cov_outer with the classes tiled instead of capped: the same
+ * jobs, the same cov (nb x nc x nc contiguous, sample stride nc*nc), nc >= 1 with no cap
+ * (a CIFAR-100 or ImageNet head).  T_r (or s_j[b] and V) come from the same launches as in
+ * those calls, over all nb*nc rows at once; a sample's block is then cut into 64x64 class
+ * tiles and every tile pair ti >= tj is the joint calls' Gram tile on that sample's rows:
+ *   kfac_kron_cov_tiled        cov[b][c][c'] (+)= sum_j < T_{j,b,c} , T_{j,b,c'} >_F
+ *   kfac_kron_cov_outer_tiled  cov[b]        (+)= sum_j s_j[b] * V_{j,b} V_{j,b}^T
+ * K (nA*nG, or nG) is cut into 2048-long segments that depend on K alone; a tile is summed
+ * over a segment in fp32 (MFMA, exact products, k-ordered), the partials over segments in
+ * segment order, (outer: times s_j[b], summed over its 64-column tiles in tile order,) over
+ * jobs in job order, all in fp64, without atomics.  Hence: two calls give identical bits;
+ * every block is bitwise symmetric (the lower triangle is computed and mirrored); diagonal
+ * entries are >= 0; a sample's block depends on that sample only, so chunking the samples
+ * changes no bit; and kfac_kron_cov_tiled's block b has exactly the bits of block (b, b) of
+ * kfac_kron_cov_joint on the same jobs (one Gram body, segmentation and reduce order).
+ * accumulate: cov += the sum, else cov = it.  At most 8 jobs per call; nb*nc, rows*nG,
+ * rows*nA as in the calls above, and the Gram launch's task count (nb x segments x tile
+ * pairs, summed over the jobs) must fit 31 bits.  Workspace per job: U and T (dense) or
+ * the row-norm partials and V (outer), plus nb * ceil(K/2048) * t(t+1)/2 partials of
+ * 64x64 floats, t = ceil(nc/64).                                                     */
+KFAC_API size_t kfac_kron_cov_tiled_workspace_bytes(const kfac_cov_job* jobs, int njobs, int64_t nb,
+                                                    int nc);
+KFAC_API int kfac_kron_cov_tiled(const kfac_cov_job* jobs, int njobs, int64_t nb, int nc, int accumulate,
+                                 float* cov, void* workspace, size_t workspace_bytes,
+                                 kfac_stream_t stream);
+KFAC_API size_t kfac_kron_cov_outer_tiled_workspace_bytes(const kfac_cov_outer_job* jobs, int njobs,
+                                                          int64_t nb, int nc);
+KFAC_API int kfac_kron_cov_outer_tiled(const kfac_cov_outer_job* jobs, int njobs, int64_t nb, int nc,
+                                       int accumulate, float* cov, void* workspace,
+                                       size_t workspace_bytes, kfac_stream_t stream);
+
 /* ------------------------------ GLM predictive covariance over a damping grid
  * With A = VA diag(lamA) VA^T and G = VG diag(lamG) VG^T (kfac_syev), kfac_invert's
  * factors satisfy L_A L_A^T = VA diag(wA) VA^T, wA[i] = 1 / (sqrt(s) lamA[i] + sqrt(n)),
