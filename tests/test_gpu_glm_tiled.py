@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import glm_joint_cases as C
+from glm_exact_cases import sparse_signs as _sparse_signs
 
 pytestmark = pytest.mark.gpu
 
@@ -100,16 +101,6 @@ def test_outer_tiled_dense_factors(hip_device, shape):
 
 # ------------------------------------------------------------------ integer-exact
 LIMIT = 1 << 24
-
-
-def _sparse_signs(rng, n, lower):
-    """n x n with at most three +-1 per column (on and below the diagonal if lower)."""
-    K = np.zeros((n, n), dtype=np.int64)
-    for c in range(n):
-        first = c if lower else 0
-        rows = rng.choice(np.arange(first, n), size=min(3, n - first), replace=False)
-        K[rows, c] = rng.choice([-1, 1], size=rows.size)
-    return K
 
 
 def _int_dense_ref(J, nA, nG, K1, K2):
