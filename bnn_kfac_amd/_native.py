@@ -78,6 +78,14 @@ class CovOuterJob(ctypes.Structure):
                 ("K2", c_vp), ("ld2", c_i64), ("lower1", c_i32), ("lower2", c_i32)]
 
 
+class DrawJob(ctypes.Structure):
+    _fields_ = [("rows", CovJob), ("Z", c_vp), ("ldZ", c_i64)]
+
+
+class DrawOuterJob(ctypes.Structure):
+    _fields_ = [("rows", CovOuterJob), ("Z", c_vp), ("ldZ", c_i64)]
+
+
 class CovConvRowsJob(ctypes.Structure):
     _fields_ = [("x", Operand), ("D", c_vp), ("ldD", c_i64), ("nG", c_i32), ("reserved", c_i32),
                 ("M", c_vp), ("ldM", c_i64)]
@@ -189,6 +197,16 @@ SIGNATURES = {
     "kfac_kron_cov_outer_tiled": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64,
                                                  ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_size_t,
                                                  c_vp]),
+    "kfac_glm_draws_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DrawJob), ctypes.c_int, c_i64,
+                                                         ctypes.c_int, c_i64]),
+    "kfac_glm_draws": (ctypes.c_int, [ctypes.POINTER(DrawJob), ctypes.c_int, c_i64, ctypes.c_int, c_i64,
+                                      ctypes.c_int, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_glm_draws_outer_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DrawOuterJob), ctypes.c_int,
+                                                               c_i64, ctypes.c_int, c_i64]),
+    "kfac_glm_draws_outer": (ctypes.c_int, [ctypes.POINTER(DrawOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                            c_i64, ctypes.c_int, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_softmax_mc": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
+                                       c_vp, c_vp, c_vp]),
     "kfac_kron_cov_sweep_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovSweepJob), ctypes.c_int,
                                                               c_i64, ctypes.c_int, ctypes.c_int]),
     "kfac_kron_cov_sweep": (ctypes.c_int, [ctypes.POINTER(CovSweepJob), ctypes.c_int, c_i64, ctypes.c_int,
@@ -656,6 +674,73 @@ def kron_cov_outer_tiled(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: 
     ws = workspace.get(out.device, need)
     check(L.kfac_kron_cov_outer_tiled(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws),
                                       ws.numel(), stream_handle(out.device)), "kfac_kron_cov_outer_tiled")
+
+
+def glm_draws_workspace_bytes(jobs, nb: int, nc: int, ns: int) -> int:
+    return lib().kfac_glm_draws_workspace_bytes(as_array(DrawJob, jobs), len(jobs), nb, nc, ns)
+
+
+def glm_draws_outer_workspace_bytes(jobs, nb: int, nc: int, ns: int) -> int:
+    return lib().kfac_glm_draws_outer_workspace_bytes(as_array(DrawOuterJob, jobs), len(jobs), nb, nc, ns)
+
+
+def _draws_out(out: torch.Tensor, nb: int, nc: int, ns: int, what: str):
+    """The draw calls write ns rows of nb*nc floats, out.stride(0) apart: refuse a view they
+    would write outside of."""
+    R = nb * nc
+    if out.dim() != 2 or out.shape[0] < ns or out.shape[1] < R or out.stride(1) != 1 or \
+            (ns > 1 and out.stride(0) < R):
+        raise ValueError(f"{what}: out must be 2-D, at least ({ns}, {R}), with unit column stride, got "
+                         f"{tuple(out.shape)} / {out.stride()}")
+    require_device(out, what)
+
+
+def glm_draws(jobs, nb: int, nc: int, ns: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_glm_draws: out (ns, >= nb*nc) with unit column stride (+)= sum_j Z_j T_j^T, <= 8 jobs
+    per call."""
+    _draws_out(out, nb, nc, ns, "glm_draws")
+    L = lib()
+    arr = as_array(DrawJob, jobs)
+    need = L.kfac_glm_draws_workspace_bytes(arr, len(jobs), nb, nc, ns)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_glm_draws(arr, len(jobs), nb, nc, ns, int(accumulate), ptr(out), max(out.stride(0), nb * nc),
+                           ptr(ws), ws.numel(), stream_handle(out.device)), "kfac_glm_draws")
+
+
+def glm_draws_outer(jobs, nb: int, nc: int, ns: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_glm_draws_outer: out (ns, >= nb*nc) (+)= sum_j u_b^T Z_{j,s} v_r, <= 8 jobs per call."""
+    _draws_out(out, nb, nc, ns, "glm_draws_outer")
+    L = lib()
+    arr = as_array(DrawOuterJob, jobs)
+    need = L.kfac_glm_draws_outer_workspace_bytes(arr, len(jobs), nb, nc, ns)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_glm_draws_outer(arr, len(jobs), nb, nc, ns, int(accumulate), ptr(out),
+                                 max(out.stride(0), nb * nc), ptr(ws), ws.numel(),
+                                 stream_handle(out.device)), "kfac_glm_draws_outer")
+
+
+def softmax_mc(mean: torch.Tensor, draws: torch.Tensor, psum: torch.Tensor, hsum: torch.Tensor,
+               accumulate: bool = False):
+    """kfac_softmax_mc: psum (nb, nc) and hsum (nb,) fp64 (+)= the sums over the ns draws of
+    softmax(mean + draws[s]) and of its entropy.  mean (nb, nc) and draws (ns, nb, nc) fp32 with
+    unit innermost stride; draws[s] is one contiguous block, the draws draws.stride(0) apart."""
+    require_device(mean, "mean")
+    require_device(draws, "draws")
+    if mean.dim() != 2 or draws.dim() != 3 or tuple(draws.shape[1:]) != tuple(mean.shape):
+        raise ValueError(f"mean {tuple(mean.shape)} / draws {tuple(draws.shape)}: expected (nb, nc) and "
+                         f"(ns, nb, nc)")
+    ns, nb, nc = draws.shape
+    if mean.stride(1) != 1 or (nb > 1 and mean.stride(0) < nc):
+        mean = mean.contiguous()
+    if not draws[0].is_contiguous() or (ns > 1 and draws.stride(0) < nb * nc):
+        draws = draws.contiguous()
+    for t, shape, what in ((psum, (nb, nc), "psum"), (hsum, (nb,), "hsum")):
+        if not t.is_cuda or t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{what}: expected a contiguous float64 {shape} tensor on the device, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    check(lib().kfac_softmax_mc(ptr(mean), mean.stride(0) if nb > 1 else nc, ptr(draws),
+                                draws.stride(0) if ns > 1 else nb * nc, ns, nb, nc, int(accumulate),
+                                ptr(psum), ptr(hsum), stream_handle(mean.device)), "kfac_softmax_mc")
 
 
 def kron_cov_sweep_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:

@@ -5,7 +5,8 @@
 // weighted Gram of a staged segment for a group of grid points; and what the joint calls
 // (covariance_joint.hip) take from both: the argument blocks of the apply / V launches, the
 // Abar^T panel, and the 64x64 Gram tile all three of their operands go through; the
-// class-tiled per-sample calls (covariance_tiled.hip) run that tile on one sample's rows.
+// class-tiled per-sample calls (covariance_tiled.hip) run that tile on one sample's rows; the
+// draw calls (covariance_draws.hip) start from the same apply / U / V launches.
 #pragma once
 
 #include "kfac_common.h"
@@ -241,6 +242,9 @@ int cov_launch_apply(const CovArgs& args, hipStream_t s);
 int cov_launch_outer_v(const OuterArgs& args, int64_t nv, hipStream_t s);
 // kfac_cov_rownorm (covariance_outer.hip) on a filled block: norm[tile][b], nn tasks.
 int cov_launch_rownorm(const OuterArgs& args, int64_t nn, hipStream_t s);
+// kfac_cov_outer_u (covariance_joint.hip) on a filled block: U = Abar K1 (nb x nA) at
+// OuterJobDev::norm, nn tasks (the row-norm launch's ranges).
+int cov_launch_outer_u(const OuterArgs& args, int64_t nn, hipStream_t s);
 // kfac_cov_sweep_reduce (covariance.hip) on a block whose njobs, nc, nb, accumulate, cov and
 // the jobs' partial (ntau x nb x nseg x nc*nc) / nseg are filled.
 int cov_launch_sweep_reduce(const CovArgs& args, int ntau, hipStream_t s);
@@ -296,6 +300,10 @@ static inline bool cov_job_ok(const kfac_cov_job& q) {
 static inline int64_t outer_nA(const kfac_cov_outer_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
 static inline size_t outer_v_bytes(const kfac_cov_outer_job& j, int64_t rows) {
   return align_up((size_t)rows * (size_t)j.nG * sizeof(float), 256);
+}
+// U = Abar K1 (nb x nA): kfac_cov_outer_u's output
+static inline size_t outer_u_bytes(const kfac_cov_outer_job& j, int64_t nb) {
+  return align_up((size_t)nb * (size_t)outer_nA(j) * sizeof(float), 256);
 }
 static inline size_t outer_norm_bytes(const kfac_cov_outer_job& j, int64_t nb) {
   return align_up((size_t)(cdiv(outer_nA(j), TILE) * nb) * sizeof(float), 256);

@@ -137,6 +137,13 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_u(OuterArgs args) {
   }
 }
 
+// The U launch alone (kfac_glm_draws_outer contracts U with the draws, not with itself).
+int cov_launch_outer_u(const OuterArgs& args, int64_t nn, hipStream_t s) {
+  hipLaunchKernelGGL(kfac_cov_outer_u, dim3((unsigned)nn), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}
+
 static int64_t joint_nseg(int64_t K) { return cdiv(K, JSEG); }
 static int64_t joint_npairs(int64_t rows) {
   const int64_t t = cdiv(rows, TILE);
@@ -144,9 +151,6 @@ static int64_t joint_npairs(int64_t rows) {
 }
 static size_t joint_partial_bytes(int64_t rows, int64_t K) {
   return align_up((size_t)(joint_npairs(rows) * joint_nseg(K)) * JTILE2 * sizeof(float), 256);
-}
-static size_t outer_u_bytes(const kfac_cov_outer_job& j, int64_t nb) {
-  return align_up((size_t)nb * (size_t)outer_nA(j) * sizeof(float), 256);
 }
 // R = nb*nc with 32-bit rows and at most JMAXT row tiles, or 0
 static int64_t joint_rows(int64_t nb, int nc) {

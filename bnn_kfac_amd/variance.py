@@ -17,7 +17,7 @@ from __future__ import annotations
 import contextlib
 import math
 from collections import OrderedDict
-from typing import Iterable, List, Sequence, Tuple
+from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -1249,6 +1249,239 @@ def efb_log_det_sweep(efb, dampings) -> Tensor:
             raise np.linalg.LinAlgError("efb_log_det_sweep: multiply * eigenvalue + add is not positive")
         out += r.log().sum(dim=1)
     return out
+
+
+# ------------------------------------------------------------ Monte-Carlo GLM predictive
+# A weight draw S = K1 Z K2^T moves the linearised logits by < T_r, Z >_F, T_r = K1^T M_r K2
+# (kfac_glm_draws / kfac_glm_draws_outer): joint draws of the logits of all inputs, with
+# glm_predictive(joint=True)'s covariance, without a weight sample or a forward pass per draw.
+def _draw_z(z: Tensor, nA: int, nG: int, ns, index: int):
+    """(z as (ns, nA, nG) with each draw one contiguous block, its draw stride)."""
+    z = z.detach()
+    if z.dim() != 3 or tuple(z.shape[1:]) != (nA, nG) or (ns is not None and z.shape[0] != ns):
+        raise ValueError(f"z[{index}] {tuple(z.shape)}: expected ({'ns' if ns is None else ns}, {nA}, {nG})")
+    N.require_device(z, f"z[{index}]")
+    if z.shape[0] == 0:
+        raise ValueError("no draws")
+    if z.stride(2) != 1 or (nA > 1 and z.stride(1) != nG) or (z.shape[0] > 1 and z.stride(0) < nA * nG):
+        z = z.contiguous()
+    return z, (z.stride(0) if z.shape[0] > 1 else nA * nG)
+
+
+def _run_draws(jobs, zs, struct, rows_struct, job_at, workspace_bytes, call, nb, nc, device,
+               max_workspace_bytes):
+    """What the two draw calls share: the (ns, nb, nc) result, jobs folded in groups of 8 with
+    `accumulate`, the draws and then the samples halved until a call's scratch fits
+    `max_workspace_bytes` (F[s][r] depends on draw s and row r only: no bit changes)."""
+    ns = zs[0][0].shape[0]
+    R = nb * nc
+    out = torch.empty(ns, R, dtype=torch.float32, device=device)
+    if nb == 0:
+        return out.view(ns, nb, nc)
+    groups = [list(zip(jobs[i:i + 8], zs[i:i + 8])) for i in range(0, len(jobs), 8)]
+
+    def build(g, b0, s0):
+        return [struct(rows_struct(*job_at(j, b0, nc)), z.data_ptr() + 4 * s0 * ldz, ldz) for j, (z, ldz) in g]
+
+    def need(n, m):
+        return max(workspace_bytes(build(g, 0, 0), n, nc, m) for g in groups)
+
+    bstep, sstep = nb, ns
+    while need(bstep, sstep) > max_workspace_bytes:
+        if sstep > 1:
+            sstep = (sstep + 1) // 2
+        elif bstep > 1:
+            bstep = (bstep + 1) // 2
+        else:
+            raise ValueError(f"one sample and one draw need {need(1, 1)} workspace bytes, "
+                             f"max_workspace_bytes is {max_workspace_bytes}")
+    if need(bstep, sstep) == 0:
+        raise ValueError(f"nb = {nb}, nc = {nc}, ns = {ns}: sizes beyond one call")
+    for b0 in range(0, nb, bstep):
+        n = min(bstep, nb - b0)
+        for s0 in range(0, ns, sstep):
+            m = min(sstep, ns - s0)
+            for gi, g in enumerate(groups):
+                call(build(g, b0, s0), n, nc, m, out[s0:s0 + m, b0 * nc:(b0 + n) * nc], accumulate=gi > 0)
+    return out.view(ns, nb, nc)
+
+
+def kron_draws(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], z: Sequence[Tensor], lower: bool = True,
+               max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """Logit draws from Jacobian rows: F[s, b, c] = sum_l < J_l[b, c] , K1_l z_l[s] K2_l^T >_F, what
+    the weight draw K1 z K2^T (KFAC.sample's, from the same z) does to the linearised outputs.
+
+    terms as kron_covariance_joint takes them; z[l] (ns, nA_l, nG_l) fp32, one standard-normal
+    matrix per draw and term in the sampler's layout (a slice along the draws is used in
+    place).  Returns (ns, nb, nc) fp32.  Two calls give identical bits, and F[s, b, c] depends
+    on sample b's rows and draw s only, so subsets of the samples or of the draws reproduce
+    their entries bit for bit.  More than 8 terms fold in groups of 8; the draws, then the
+    samples, are cut until a call's scratch fits `max_workspace_bytes`.
+    """
+    keep, jobs, nb, nc = _cov_jobs(terms, lower, "kron_draws")
+    if len(z) != len(jobs):
+        raise ValueError(f"{len(jobs)} terms, {len(z)} draw tensors")
+    zs = [_draw_z(zl, j[2], j[3], None if i == 0 else z[0].shape[0], i) for i, (zl, j) in enumerate(zip(z, jobs))]
+    return _run_draws(jobs, zs, N.DrawJob, N.CovJob, _cov_job_at, N.glm_draws_workspace_bytes, N.glm_draws,
+                      nb, nc, keep[0].device, max_workspace_bytes)
+
+
+def kron_draws_outer(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]], z: Sequence[Tensor],
+                     lower: bool = True, max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_draws for Linear layers without their Jacobian rows:
+    F[s, b, c] = sum_l u_l[b]^T z_l[s] v_l[b, c], U = [a | 1] K1 and V = D K2 as in
+    kron_covariance_outer_joint.  Per draw 2 nb nA nG flops and one pass over z_l[s] per 64
+    samples; no weight sample, no forward pass.
+
+    terms as kron_covariance_outer_joint takes them, z and the guarantees as in kron_draws.
+    """
+    keep, jobs, nb, nc = _cov_outer_jobs(terms, lower, "kron_draws_outer")
+    if len(z) != len(jobs):
+        raise ValueError(f"{len(jobs)} terms, {len(z)} draw tensors")
+    zs = [_draw_z(zl, j[2] + j[3], j[6], None if i == 0 else z[0].shape[0], i)
+          for i, (zl, j) in enumerate(zip(z, jobs))]
+    return _run_draws(jobs, zs, N.DrawOuterJob, N.CovOuterJob, _cov_outer_job_at,
+                      N.glm_draws_outer_workspace_bytes, N.glm_draws_outer, nb, nc, keep[0].device,
+                      max_workspace_bytes)
+
+
+def _softmax_mc_finish(psum: Tensor, hsum: Tensor, ns: int):
+    """(probs, expected_entropy, entropy, mutual_information) fp32 from the fp64 sums."""
+    probs = psum / ns
+    expected = hsum / ns
+    entropy = torch.special.entr(probs).sum(dim=1)
+    mi = (entropy - expected).clamp_min(0.0)
+    return tuple(t.to(torch.float32) for t in (probs, expected, entropy, mi))
+
+
+def softmax_mc_stats(logits: Tensor, draws: Tensor):
+    """Monte-Carlo softmax statistics of logits (N, nc) + draws (S, N, nc) by kfac_softmax_mc:
+    (probs (N, nc), expected_entropy (N,), entropy (N,), mutual_information (N,)), fp32.
+    probs = mean_s softmax(logits + draws[s]); expected_entropy = mean_s H(softmax(.)) in nats;
+    entropy = H(probs); mutual_information = entropy - expected_entropy (the epistemic part),
+    finalised in fp64 from the device's fp64 sums and clamped at 0."""
+    ns, nb, nc = draws.shape
+    psum = torch.empty(nb, nc, dtype=torch.float64, device=logits.device)
+    hsum = torch.empty(nb, dtype=torch.float64, device=logits.device)
+    N.softmax_mc(logits.detach(), draws.detach(), psum, hsum)
+    return _softmax_mc_finish(psum, hsum, ns)
+
+
+class GLMPredictiveMC(NamedTuple):
+    logits: Tensor
+    probs: Tensor
+    entropy: Tensor
+    expected_entropy: Tensor
+    mutual_information: Tensor
+    draws: Optional[Tensor]
+
+
+def glm_predictive_mc(curv, x: Tensor, n_draws: int = 100, layers: Iterable = None, chunk: int = 64,
+                      jacobians: str = "factored", generator: torch.Generator = None,
+                      z: Sequence[Tensor] = None, max_draw_bytes: int = 1 << 30,
+                      return_draws: bool = False) -> GLMPredictiveMC:
+    """The Monte-Carlo GLM predictive of `curv.model`: `n_draws` posterior weight draws applied to
+    the linearised network at every x, and the softmax statistics of the resulting logits --
+    what `n_draws` x (sample_and_replace() + a forward pass) gives for a network that is linear
+    in its weights, without a weight sample or a forward pass per draw.
+
+    Returns (logits (N, nc), probs (N, nc), entropy (N,), expected_entropy (N,),
+    mutual_information (N,), draws): softmax_mc_stats' quantities; `draws` is the
+    (n_draws, N, nc) logit perturbations when `return_draws`, else None (they then exist one
+    (draw chunk, sample chunk) block at a time).  Draw s is ONE weight sample applied to every
+    x (the draws are jointly consistent across the inputs; their covariance is
+    glm_predictive(joint=True)'s).  A regression net (nc = 1) has its use in `draws`; its
+    statistics are the degenerate probs = 1, entropies 0.
+
+    curv: a KFAC (factors inv_state, lower-triangular) or an EFB (K1 = V_A, K2 = V_G dense,
+    z scaled elementwise by inv_state^T, as EFB.sample draws).  Routes as in glm_predictive:
+    "factored" sends Linear layers through kron_draws_outer and Conv2d rows (_conv_rows) through
+    kron_draws; "dense" sends output_jacobians' rows through kron_draws.
+
+    The standard-normal z are drawn per draw chunk, for the layers in `layers` order (default:
+    model.modules() order), each as torch.randn(chunk_draws, nA, nG, generator=generator) on the
+    model's device; an explicit `z` -- a list of per-layer (n_draws, nA, nG) tensors in that
+    order -- replaces them and is sliced, not copied (EFB: scaled into a new tensor).  A draw
+    chunk holds as many draws as keep the live z within `max_draw_bytes`.  The samples go
+    through `chunk` at a time inside each draw chunk, so with more than one draw chunk the
+    captures (or Jacobians) of a sample chunk are recomputed per draw chunk; the generator is
+    never replayed.  Chunking either way changes no bit of a draw."""
+    if jacobians not in ("dense", "factored"):
+        raise ValueError(f"jacobians must be 'dense' or 'factored', got {jacobians!r}")
+    if n_draws < 1:
+        raise ValueError(f"n_draws must be at least 1, got {n_draws}")
+    assert curv.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
+    model = curv.model
+    efb = hasattr(curv, "eigvecs")
+    if layers is None:
+        layers = [m for m in list(model.modules())[1:] if m in curv.state]
+    layers = list(layers)
+    factors = {layer: tuple(curv.eigvecs[layer] if efb else curv.inv_state[layer]) for layer in layers}
+    shapes = [(factors[layer][0].shape[0], factors[layer][1].shape[0]) for layer in layers]
+    if z is not None:
+        z = list(z)
+        if len(z) != len(layers):
+            raise ValueError(f"{len(layers)} layers, {len(z)} draw tensors")
+        for i, (zl, (nA, nG)) in enumerate(zip(z, shapes)):
+            if tuple(zl.shape) != (n_draws, nA, nG):
+                raise ValueError(f"z[{i}] {tuple(zl.shape)}: expected ({n_draws}, {nA}, {nG})")
+    per_draw = 4 * sum(nA * nG for nA, nG in shapes)
+    step = max(1, min(n_draws, max_draw_bytes // max(per_draw, 1)))
+    N_, device = x.shape[0], factors[layers[0]][0].device
+    logits, draws, psum, hsum = [], None, None, None
+    for s0 in range(0, n_draws, step):
+        m = min(step, n_draws - s0)
+        if z is None:
+            zc = [torch.randn(m, nA, nG, generator=generator, device=device, dtype=torch.float32)
+                  for nA, nG in shapes]
+            if efb:
+                for zl, layer in zip(zc, layers):
+                    zl *= curv.inv_state[layer].detach().t()
+        else:
+            zc = [zl[s0:s0 + m] for zl in z]
+            if efb:
+                zc = [zl * curv.inv_state[layer].detach().t() for zl, layer in zip(zc, layers)]
+        for c0 in range(0, N_, chunk):
+            xc = x[c0:c0 + chunk]
+            outer, dense, zo, zd = [], [], [], []
+            if jacobians == "dense":
+                f, Js = output_jacobians(model, layers, xc)
+                dense = [(J, *factors[layer]) for layer, J in zip(layers, Js)]
+                zd = zc
+            else:
+                f, io = layer_io_jacobians(model, layers, xc)
+                for layer, (a, D), zl in zip(layers, io, zc):
+                    if isinstance(layer, torch.nn.Linear):
+                        if a.dim() != 2:
+                            raise ValueError(f"the factored route needs 2-D Linear inputs, got {tuple(a.shape)}")
+                        outer.append((a, D, *factors[layer]))
+                        zo.append(zl)
+                    elif isinstance(layer, torch.nn.Conv2d):
+                        dense.append((_conv_rows(layer, a, D), *factors[layer]))
+                        zd.append(zl)
+                    else:
+                        raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
+                                         f"{layer.__class__.__name__}")
+            F = kron_draws_outer(outer, zo, lower=not efb) if outer else None
+            if dense:
+                rows = kron_draws(dense, zd, lower=not efb)
+                F = rows if F is None else F + rows
+            n, nc = f.shape
+            if psum is None:
+                psum = torch.empty(N_, nc, dtype=torch.float64, device=device)
+                hsum = torch.empty(N_, dtype=torch.float64, device=device)
+                if return_draws:
+                    draws = torch.empty(n_draws, N_, nc, dtype=torch.float32, device=device)
+            if s0 == 0:
+                logits.append(f)
+            N.softmax_mc(f.contiguous(), F, psum[c0:c0 + n], hsum[c0:c0 + n], accumulate=s0 > 0)
+            if return_draws:
+                draws[s0:s0 + m, c0:c0 + n] = F
+        del zc
+    if psum is None:  # no samples
+        raise ValueError("x holds no samples")
+    stats = _softmax_mc_finish(psum, hsum, n_draws)
+    return GLMPredictiveMC(torch.cat(logits), stats[0], stats[2], stats[1], stats[3], draws)
 
 
 def probit_predictive(logits: Tensor, cov: Tensor) -> Tensor:

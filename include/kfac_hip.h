@@ -402,6 +402,72 @@ KFAC_API int kfac_kron_cov_outer_tiled(const kfac_cov_outer_job* jobs, int njobs
                                        int accumulate, float* cov, void* workspace,
                                        size_t workspace_bytes, kfac_stream_t stream);
 
+/* --------------------------- GLM Monte-Carlo predictive: logit draws, softmax statistics
+ * A posterior weight draw is S = K1 Z K2^T (kfac_sample; Z is its z, index a*nG + g), and
+ * the linearised network is linear in the weights, so draw s moves logit row r = b*nc + c by
+ *   F[s][r] (+)= sum_j < M_{j,r} , K1_j Z_{j,s} K2_j^T >_F = sum_j < T_{j,r} , Z_{j,s} >_F ,
+ * T_r = K1^T M_r K2 the projected row of the covariance calls: exactly what kfac_sample's
+ * draw from Z_s would do to the linearised logits, jointly for all samples of the call (one
+ * draw is one weight sample), with covariance kfac_kron_cov_joint's.  No Cholesky of the
+ * covariance, no weight sample, no forward pass; any nc, any rank.
+ *   kfac_glm_draws        rows given (Conv2d rows, dense Jacobians): T by the projection of
+ *                         kfac_kron_cov_joint, then F = Z T^T over K = nA*nG
+ *   kfac_glm_draws_outer  Linear layers, no row formed: T_r = u_b v_r^T, so
+ *                         F[s][r] = u_b^T Z_s v_r with U = Abar K1 (nb x nA) and
+ *                         V = Delta K2 (R x nG), kfac_kron_cov_outer_joint's U and V;
+ *                         per draw 2*nb*nA*nG flops, Z read once per 64 samples
+ * Z_s is nA*nG elements at Z + s*ldZ (ldZ >= nA*nG), the draw in kfac_sample's order.
+ * F[s][r] is at F + s*ldF + r, R = nb*nc, ldF >= R; columns >= R are never touched.
+ * accumulate: F += the sum over jobs, else F = it.
+ * Sums: a 64x64 tile over one 2048-long segment of K = nA*nG (rows given), or W = U Z_s over
+ * all of nA and then W V over one 64-column tile of nG (outer), in fp32 (MFMA, exact
+ * products, k-ordered); the segments (g-tiles) in order and the jobs in job order in fp64;
+ * no atomics.  The cut points depend on nA and nG alone.  Hence: two calls give identical
+ * bits; F[s][r] depends on row r's inputs, draw s, the factors and the job shapes only --
+ * not on nb or ns, nor on where the sample sits in the call or the draw sits in Z -- so
+ * chunking the samples or the draws changes no bit.
+ * At most 8 jobs per call; nc >= 1 and ns >= 1 have no cap; R, ns, rows*nG, rows*nA and
+ * every launch's task count must fit 31 bits.  KFAC_EINVAL: null pointers, pitches below
+ * the widths, njobs outside 1..8, nb, nc or ns < 1, ldF < R; KFAC_EWORKSPACE: a workspace
+ * below the query's answer.  All of it is checked before any launch.  Workspace per job:
+ * U and T (rows given) plus ceil(K/2048) x ceil(R/64) x ceil(ns/64) tiles of 64x64 floats;
+ * U, V, V^T (outer) plus ns x ceil(nG/64) x R floats.                                   */
+typedef struct kfac_draw_job { /* rows given: Conv2d rows, dense Jacobians */
+  kfac_cov_job rows; /* J, K1, K2, lower1/2 exactly as kfac_kron_cov_joint takes them */
+  const float* Z;    /* draw s at Z + s*ldZ: nA*nG elements, index a*nG + g (kfac_sample's z) */
+  int64_t ldZ;
+} kfac_draw_job;
+
+typedef struct kfac_draw_outer_job { /* Linear layers, no row formed */
+  kfac_cov_outer_job rows; /* a, D, K1, K2 exactly as kfac_kron_cov_outer_joint takes them */
+  const float* Z;
+  int64_t ldZ;
+} kfac_draw_outer_job;
+
+KFAC_API size_t kfac_glm_draws_workspace_bytes(const kfac_draw_job* jobs, int njobs, int64_t nb, int nc,
+                                               int64_t ns);
+KFAC_API int kfac_glm_draws(const kfac_draw_job* jobs, int njobs, int64_t nb, int nc, int64_t ns,
+                            int accumulate, float* F, int64_t ldF, void* workspace, size_t workspace_bytes,
+                            kfac_stream_t stream);
+KFAC_API size_t kfac_glm_draws_outer_workspace_bytes(const kfac_draw_outer_job* jobs, int njobs, int64_t nb,
+                                                     int nc, int64_t ns);
+KFAC_API int kfac_glm_draws_outer(const kfac_draw_outer_job* jobs, int njobs, int64_t nb, int nc, int64_t ns,
+                                  int accumulate, float* F, int64_t ldF, void* workspace,
+                                  size_t workspace_bytes, kfac_stream_t stream);
+
+/* The softmax statistics of the draws: with y_s = mean[b] + F[s][b] (nc logits),
+ *   psum[b][c] (+)= sum_s softmax(y_s)[c] ,   hsum[b] (+)= sum_s H(softmax(y_s))   (nats),
+ * H = log sum_c e^y - sum_c p_c y after subtracting the row maximum.  mean is nb x nc with
+ * row stride ldm >= nc, F as above (ldF >= nb*nc), psum nb x nc and hsum nb contiguous fp64.
+ * Evaluated in fp64 from the fp32 inputs (exp and log in fp64: logits of +-80 neither
+ * overflow nor give NaN), the draws summed in draw order; one launch, no workspace, no
+ * atomics, any nc.  accumulate: the running sums go on from psum / hsum (the draws given in
+ * chunks change no bit against one call), else they start at 0.
+ * KFAC_EINVAL: null pointers, ns, nb or nc < 1, ldm < nc, ldF < nb*nc.                  */
+KFAC_API int kfac_softmax_mc(const float* mean, int64_t ldm, const float* F, int64_t ldF, int64_t ns,
+                             int64_t nb, int nc, int accumulate, double* psum, double* hsum,
+                             kfac_stream_t stream);
+
 /* ------------------------------ GLM predictive covariance over a damping grid
  * With A = VA diag(lamA) VA^T and G = VG diag(lamG) VG^T (kfac_syev), kfac_invert's
  * factors satisfy L_A L_A^T = VA diag(wA) VA^T, wA[i] = 1 / (sqrt(s) lamA[i] + sqrt(n)),
