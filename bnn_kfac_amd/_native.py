@@ -115,6 +115,19 @@ class CovOuterFullJob(ctypes.Structure):
                 ("VG", c_vp), ("ldG", c_i64), ("W", c_vp), ("ldW", c_i64)]
 
 
+class InfCovJob(ctypes.Structure):
+    _fields_ = [("J", c_vp), ("ldJ", c_i64), ("nA", c_i32), ("nG", c_i32), ("UA", c_vp),
+                ("ldA", c_i64), ("ra", c_i32), ("UG", c_vp), ("ldG", c_i64), ("rg", c_i32),
+                ("W", c_vp), ("ldW", c_i64), ("F", c_vp), ("ldF", c_i64)]
+
+
+class InfCovOuterJob(ctypes.Structure):
+    _fields_ = [("a", c_vp), ("lda", c_i64), ("cols", c_i32), ("has_ones", c_i32), ("D", c_vp),
+                ("ldD", c_i64), ("nG", c_i32), ("reserved", c_i32), ("UA", c_vp), ("ldA", c_i64),
+                ("ra", c_i32), ("UG", c_vp), ("ldG", c_i64), ("rg", c_i32), ("W", c_vp),
+                ("ldW", c_i64), ("F", c_vp), ("ldF", c_i64)]
+
+
 class SampleJob(ctypes.Structure):
     _fields_ = [("LA", c_vp), ("ldA", c_i64), ("LG", c_vp), ("ldG", c_i64), ("Z", c_vp),
                 ("nA", c_i32), ("nG", c_i32), ("W", c_vp), ("ldW", c_i64), ("bias", c_vp),
@@ -227,6 +240,14 @@ SIGNATURES = {
     "kfac_kron_cov_outer_full": (ctypes.c_int, [ctypes.POINTER(CovOuterFullJob), ctypes.c_int, c_i64,
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                                 ctypes.c_size_t, c_vp]),
+    "kfac_inf_cov_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(InfCovJob), ctypes.c_int, c_i64,
+                                                       ctypes.c_int]),
+    "kfac_inf_cov": (ctypes.c_int, [ctypes.POINTER(InfCovJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                    ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_inf_cov_outer_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(InfCovOuterJob), ctypes.c_int,
+                                                             c_i64, ctypes.c_int]),
+    "kfac_inf_cov_outer": (ctypes.c_int, [ctypes.POINTER(InfCovOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                          ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "kfac_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SampleJob), ctypes.c_int]),
     "kfac_sample": (ctypes.c_int, [ctypes.POINTER(SampleJob), ctypes.c_int, ctypes.c_int, c_vp,
                                    ctypes.c_size_t, c_vp]),
@@ -800,6 +821,35 @@ def kron_cov_outer_full(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accu
     ws = workspace.get(out.device, need)
     check(L.kfac_kron_cov_outer_full(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws),
                                      ws.numel(), stream_handle(out.device)), "kfac_kron_cov_outer_full")
+
+
+def inf_cov_workspace_bytes(jobs, nb: int, nc: int) -> int:
+    return lib().kfac_inf_cov_workspace_bytes(as_array(InfCovJob, jobs), len(jobs), nb, nc)
+
+
+def inf_cov(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_inf_cov: out (nb, nc, nc) (+)= sum_j [rows' W-weighted Gram - Gram of F t], <= 8 jobs."""
+    L = lib()
+    arr = as_array(InfCovJob, jobs)
+    need = L.kfac_inf_cov_workspace_bytes(arr, len(jobs), nb, nc)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_inf_cov(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
+                         stream_handle(out.device)), "kfac_inf_cov")
+
+
+def inf_cov_outer_workspace_bytes(jobs, nb: int, nc: int) -> int:
+    return lib().kfac_inf_cov_outer_workspace_bytes(as_array(InfCovOuterJob, jobs), len(jobs), nb, nc)
+
+
+def inf_cov_outer(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_inf_cov_outer: out (nb, nc, nc) (+)= sum_j [Delta diag(rho) Delta^T - Gram of F t],
+    <= 8 jobs."""
+    L = lib()
+    arr = as_array(InfCovOuterJob, jobs)
+    need = L.kfac_inf_cov_outer_workspace_bytes(arr, len(jobs), nb, nc)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_inf_cov_outer(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
+                               stream_handle(out.device)), "kfac_inf_cov_outer")
 
 
 def sample(jobs, device: torch.device, accumulate: bool) -> None:

@@ -120,12 +120,13 @@ struct SweepArgs {
 // (the B fragment scaled by its k-row's weight: one multiply per MFMA and tau), so slice
 // tau does not depend on nt or on its place in the group.  The four wave partials are
 // summed in cov_gram_segment's fixed order.  Loads are unconditional (clamped index).
+// ldT: the stride between the sample's rows where they are not K apart (0: K).
 enum WGramMode { WGRAM_VECTOR = 0, WGRAM_RANK1 = 1, WGRAM_FLAT = 2 };
 
 template <WGramMode MODE>
 __device__ __forceinline__ void cov_wgram_segment(const float* Tb, int64_t K, int nc, int64_t k0,
                                                   const SweepWeights& W, int nG, int nt, float* part,
-                                                  int64_t part_stride, float* lds) {
+                                                  int64_t part_stride, float* lds, int64_t ldT = 0) {
   float* xs = lds;
   float* wl = xs + WSEG * WPITCH;
   float* red = wl + WTG * WSEG;
@@ -134,9 +135,10 @@ __device__ __forceinline__ void cov_wgram_segment(const float* Tb, int64_t K, in
   const bool live = k0 + tid < K;
   const int64_t kc = live ? k0 + tid : K - 1;
   const float* src = Tb + kc;
+  const int64_t rs = ldT ? ldT : K;
 #pragma unroll 8
   for (int c = 0; c < 32; ++c) {
-    const float x = src[(int64_t)min(c, nc - 1) * K];
+    const float x = src[(int64_t)min(c, nc - 1) * rs];
     xs[tid * WPITCH + c] = (live && c < nc) ? x : 0.f;
   }
   int64_t ia = 0, ig = kc;

@@ -1251,6 +1251,219 @@ def efb_log_det_sweep(efb, dampings) -> Tensor:
     return out
 
 
+# ------------------------------------------------------------ GLM predictive under the INF posterior
+# INF's posterior is Gaussian with precision P = s (U Lambda U^T + D+) + n I, U = kron(U_A, U_G)
+# (nA*nG x r), D+ the diagonal correction clipped at 0.  By Woodbury, with w = 1 / (s D+ + n),
+# sigma = sqrt(s Lambda), B = chol(I + sigma U^T diag(w) U sigma) and F = B^-1 diag(sigma):
+#   P^-1 = diag(w) - diag(w) U F^T F U^T diag(w) ,
+# so cov = (W-weighted Gram of the rows) - (Gram of F t), t = U_A^T (M o W) U_G
+# (kfac_inf_cov, kfac_inf_cov_outer): the posterior INF defines, exactly, with no square root
+# of the covariance and no sampling loop.  INF.sample (the reference's sampler, ported
+# literally) is left as it is.
+def _inf_shapes(UA: Tensor, UG: Tensor, W: Tensor, F: Tensor):
+    """(nA, nG, ra, rg) after the shape checks, which need no device."""
+    for U, what in ((UA, "UA"), (UG, "UG")):
+        if U.dim() != 2 or U.shape[0] == 0 or U.shape[1] == 0:
+            raise ValueError(f"{what} {tuple(U.shape)}: expected a (n, rank) matrix of eigenvectors")
+    (nA, ra), (nG, rg) = UA.shape, UG.shape
+    if tuple(W.shape) != (nA, nG):
+        raise ValueError(f"W {tuple(W.shape)}: expected ({nA}, {nG})")
+    if tuple(F.shape) != (ra * rg, ra * rg):
+        raise ValueError(f"F {tuple(F.shape)}: expected ({ra * rg}, {ra * rg})")
+    return nA, nG, ra, rg
+
+
+def _inf_operands(UA: Tensor, UG: Tensor, W: Tensor, F: Tensor):
+    """(tensors to keep alive, the job tuple's last ten fields UA, ldA, ra, ..., F, ldF)."""
+    for t, what in ((UA, "UA"), (UG, "UG"), (W, "W"), (F, "F")):
+        N.require_device(t, what)
+    # (a view goes through uncopied only if its rows have unit stride and lie at least their
+    # width apart: an expanded tensor's row stride 0 is not a leading dimension)
+    UA, UG, F = (t.detach() if t.stride(-1) == 1 and (t.shape[0] == 1 or t.stride(0) >= t.shape[1])
+                 else t.detach().contiguous() for t in (UA, UG, F))
+    W = W.detach().contiguous()
+    ld = lambda t: max(t.stride(0), t.shape[1])  # noqa: E731
+    return [UA, UG, W, F], (UA.data_ptr(), ld(UA), UA.shape[1], UG.data_ptr(), ld(UG), UG.shape[1],
+                            W.data_ptr(), W.numel(), F.data_ptr(), ld(F))
+
+
+def kron_covariance_inf(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
+                        max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """cov[b, c, c'] = sum_l [ sum_{i,g} W_l[i, g] M_l[b, c][i, g] M_l[b, c'][i, g]
+                               - < F_l t_l[b, c], F_l t_l[b, c'] > ],
+    t_l[b, c] = UA_l^T (M_l[b, c] o W_l) UG_l flattened p*rg + q: J P^-1 J^T under the INF
+    posterior (inf_covariance_factors).
+
+    terms: [(J_l, UA_l, UG_l, W_l, F_l)], J (nb, nc, nA*nG) or (nc, nA*nG) in the posterior's
+    order (posterior_jacobian), UA (nA, ra), UG (nG, rg), W (nA, nG) non-negative, F (ra*rg,
+    ra*rg).  Returns (nb, nc, nc) fp32: every block bitwise symmetric, a sample's block depends
+    on that sample only (chunking under `max_workspace_bytes` changes no bit), two calls give
+    identical bits, more than 8 terms fold in groups of 8.  The diagonal is a difference of two
+    non-negative sums and is not clamped: it may come out negative at rounding level.  Shapes
+    are checked (ValueError) before anything touches the device.
+    """
+    if not terms:
+        raise ValueError("no terms")
+    parsed = []
+    nb = nc = None
+    for J, UA, UG, W, F in terms:
+        nA, nG, _, _ = _inf_shapes(UA, UG, W, F)
+        J3, ld = _cov_rows(J, nA * nG)
+        if nb is None:
+            nb, nc = J3.shape[0], J3.shape[1]
+        elif (J3.shape[0], J3.shape[1]) != (nb, nc):
+            raise ValueError("all terms need the same (nb, nc)")
+        if nc > MAX_COV_CLASSES:
+            raise ValueError(f"kron_covariance_inf handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        parsed.append((J3, ld, nA, nG, UA, UG, W, F))
+    keep, jobs = [], []
+    for J3, ld, nA, nG, UA, UG, W, F in parsed:
+        N.require_device(J3, "J")
+        held, tail = _inf_operands(UA, UG, W, F)
+        keep.extend([J3, *held])
+        jobs.append((J3.data_ptr(), ld, nA, nG, *tail))
+    return _run_per_sample(jobs, N.InfCovJob, _cov_job_at, N.inf_cov_workspace_bytes, N.inf_cov, nb, nc,
+                           keep[0].device, max_workspace_bytes)
+
+
+def kron_covariance_outer_inf(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]],
+                              max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_inf for Linear layers without their Jacobian rows (M[b, c] =
+    [a[b] | 1] D[b, c]^T): cov[b] = sum_l [ D_l[b] diag(rho_l[b]) D_l[b]^T - Y_l[b] Y_l[b]^T ],
+    rho[b][g] = sum_i abar[b][i]^2 W[i, g], Y[b][c] = F t[b, c],
+    t[b, c][p, q] = sum_g H[b][p, g] D[b, c][g] UG[g, q], H[b][p, g] = sum_i UA[i, p] abar[b][i] W[i, g].
+
+    terms: [(a_l, D_l, UA_l, UG_l, W_l, F_l)], a (nb, cols) and D (nb, nc, nG) as
+    layer_io_jacobians returns them, UA (nA, ra) with nA = cols + 1 (bias: the ones column is
+    implicit) or nA = cols, UG, W, F as in kron_covariance_inf, whose guarantees hold.
+    """
+    if not terms:
+        raise ValueError("no terms")
+    parsed = []
+    nb = nc = None
+    for a, D, UA, UG, W, F in terms:
+        nA, nG, _, _ = _inf_shapes(UA, UG, W, F)
+        D3, ldD = _cov_rows(D, nG)
+        a2 = a.detach()
+        a2 = a2.reshape(1, -1) if a2.dim() == 1 else a2
+        if a2.dim() != 2:
+            raise ValueError(f"a {tuple(a2.shape)}: expected (nb, cols), a Linear layer's 2-D input")
+        cols = a2.shape[1]
+        if nA not in (cols, cols + 1) or cols == 0:
+            raise ValueError(f"a has {cols} columns, UA {tuple(UA.shape)} needs {nA} or {nA - 1}")
+        if nb is None:
+            nb, nc = D3.shape[0], D3.shape[1]
+        elif (D3.shape[0], D3.shape[1]) != (nb, nc):
+            raise ValueError("all terms need the same (nb, nc)")
+        if a2.shape[0] != nb:
+            raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
+        if nc > MAX_COV_CLASSES:
+            raise ValueError(f"kron_covariance_outer_inf handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        parsed.append((a2, cols, D3, ldD, nA, nG, UA, UG, W, F))
+    keep, jobs = [], []
+    for a2, cols, D3, ldD, nA, nG, UA, UG, W, F in parsed:
+        if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols):
+            a2 = a2.contiguous()
+        lda = a2.stride(0) if nb > 1 else cols
+        for t, what in ((a2, "a"), (D3, "D")):
+            N.require_device(t, what)
+        held, tail = _inf_operands(UA, UG, W, F)
+        keep.extend([a2, D3, *held])
+        jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0, *tail))
+    return _run_per_sample(jobs, N.InfCovOuterJob, _cov_outer_job_at, N.inf_cov_outer_workspace_bytes,
+                           N.inf_cov_outer, nb, nc, keep[0].device, max_workspace_bytes)
+
+
+def _inf_layer_factors(inf, add, multiply, layers):
+    """[(layer, UA, UG, d = s D+ + n (nA, nG) fp64, sigma = sqrt(s Lambda), B^-1)] from
+    `inf.state`, B = chol(I + sigma U^T diag(1/d) U sigma); inf.state is only read."""
+    from .curvatures import INF, KFAC
+    assert inf.state, "State dict is empty. Did you call 'update' prior to this?"
+    entries = list(inf.state)
+    damping = KFAC._damping(None, add, multiply, len(entries))
+    out = []
+    for layer in (entries if layers is None else list(layers)):
+        n, s = damping[entries.index(layer)]
+        UA, UG, lam, correction = inf.state[layer]
+        d = float(s) * correction.detach().to(torch.float64).clamp(min=0.0) + float(n)
+        if not bool((d > 0).all()):
+            raise np.linalg.LinAlgError("INF: multiply * correction + add is not positive")
+        sigma = (s * lam.detach()).sqrt()
+        c = d.reciprocal().sqrt().to(torch.float32)
+        vtv = N.kron_gram(UA.detach(), UG.detach(), c, sigma)
+        (B_inv,) = INF._chol_inverse((vtv + vtv.t()) / 2., (1.0,))
+        out.append((layer, UA.detach(), UG.detach(), d.reshape(UA.shape[0], UG.shape[0]), sigma, B_inv))
+    return out
+
+
+def inf_covariance_factors(inf, add=0., multiply=1., layers: Iterable = None):
+    """{layer: (UA, UG, W, F)} for kron_covariance_inf / kron_covariance_outer_inf from
+    `inf.state` (INF.update's (U_A, U_G, Lambda, D)): W = 1 / (s D+ + n) as (nA, nG) fp32,
+    computed in fp64 on the device, F = B^-1 diag(sigma) with sigma = sqrt(s Lambda) and
+    B = chol(I + sigma U^T diag(w) U sigma) (N.kron_gram, INF._chol_inverse).  `add` / `multiply`
+    are scalars or per-layer lists, as in INF.invert; no invert call is needed and `inf.state`
+    is not modified (INF.invert clips the correction in place; this does not).  Raises
+    numpy.linalg.LinAlgError where s D+ + n is not positive."""
+    return {layer: (UA, UG, d.reciprocal().to(torch.float32).contiguous(), (B_inv * sigma[None, :]).contiguous())
+            for layer, UA, UG, d, sigma, B_inv in _inf_layer_factors(inf, add, multiply, layers)}
+
+
+def inf_log_det(inf, add=0., multiply=1.) -> Tensor:
+    """log det of the INF precision P = s (U Lambda U^T + D+) + n I over every layer of
+    `inf.state`: sum_layers [ sum log(s D+ + n) - 2 sum log diag(B^-1) ] (0-dim fp64), the
+    counterpart of log_det_sweep / efb_log_det_sweep."""
+    total = None
+    for _, _, _, d, _, B_inv in _inf_layer_factors(inf, add, multiply, None):
+        term = d.log().sum() - 2.0 * B_inv.diagonal().to(torch.float64).log().sum()
+        total = term if total is None else total + term
+    return total
+
+
+def _inf_chunk(model, layers, factors, x, jacobians):
+    """(logits, cov (n, nc, nc)) of one chunk; factors[layer] = (UA, UG, W, F)."""
+    if jacobians == "dense":
+        f, Js = output_jacobians(model, layers, x)
+        return f, kron_covariance_inf([(J, *factors[layer]) for layer, J in zip(layers, Js)])
+    f, io = layer_io_jacobians(model, layers, x)
+    outer, dense = [], []
+    for layer, (a, D) in zip(layers, io):
+        if isinstance(layer, torch.nn.Linear):
+            if a.dim() != 2:
+                raise ValueError(f"the factored route needs 2-D Linear inputs, got {tuple(a.shape)}")
+            outer.append((a, D, *factors[layer]))
+        elif isinstance(layer, torch.nn.Conv2d):
+            dense.append((_conv_rows(layer, a, D), *factors[layer]))
+        else:
+            raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
+                             f"{layer.__class__.__name__}")
+    cov = kron_covariance_outer_inf(outer) if outer else None
+    if dense:
+        conv = kron_covariance_inf(dense)
+        cov = conv if cov is None else cov + conv
+    return f, cov
+
+
+def glm_predictive_inf(inf, x: Tensor, add=0., multiply=1., layers: Iterable = None, chunk: int = 64,
+                       jacobians: str = "dense"):
+    """glm_predictive under the INF posterior, straight from `inf.state` (no invert call):
+    (logits (N, nc), cov (N, nc, nc)), cov = sum_l J_l P_l^-1 J_l^T with P_l the precision
+    s (U Lambda U^T + D+) + n I of layer l, in closed form (inf_covariance_factors), in chunks
+    of `chunk` samples.  `jacobians` as in glm_predictive_efb: "dense" sends output_jacobians'
+    rows through kron_covariance_inf; "factored" sends Linear layers through
+    kron_covariance_outer_inf and Conv2d layers through kron_covariance_inf on rows formed from
+    the same captures."""
+    if jacobians not in ("dense", "factored"):
+        raise ValueError(f"jacobians must be 'dense' or 'factored', got {jacobians!r}")
+    layers = _efb_layers(inf, layers)
+    factors = inf_covariance_factors(inf, add, multiply, layers)
+    logits, covs = [], []
+    for c0 in range(0, x.shape[0], chunk):
+        f, cov = _inf_chunk(inf.model, layers, factors, x[c0:c0 + chunk], jacobians)
+        logits.append(f)
+        covs.append(cov)
+    return torch.cat(logits), torch.cat(covs)
+
+
 # ------------------------------------------------------------ Monte-Carlo GLM predictive
 # A weight draw S = K1 Z K2^T moves the linearised logits by < T_r, Z >_F, T_r = K1^T M_r K2
 # (kfac_glm_draws / kfac_glm_draws_outer): joint draws of the logits of all inputs, with

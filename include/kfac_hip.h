@@ -583,6 +583,73 @@ KFAC_API int kfac_kron_cov_outer_full(const kfac_cov_outer_full_job* jobs, int n
                                       int nt, int accumulate, float* cov, void* workspace,
                                       size_t workspace_bytes, kfac_stream_t stream);
 
+/* ------------------- GLM predictive covariance under the INF posterior
+ * INF (low-rank EFB plus a diagonal correction) is Gaussian with precision
+ *   P = s (U Lambda U^T + D+) + n I ,  U = kron(UA, UG)  (nA*nG x r, r = ra*rg).
+ * By Woodbury, with w = 1 / (s D+ + n) (nA x nG, flat order i*nG + g), sigma = sqrt(s Lambda),
+ * B = chol(I + sigma U^T diag(w) U sigma) and F = B^-1 diag(sigma) (r x r):
+ *   P^-1 = diag(w) - diag(w) U F^T F U^T diag(w) ,
+ *   cov[b][c][c'] (+)= sum_j [ sum_{i,g} W[i][g] M_{b,c}[i][g] M_{b,c'}[i][g] - < F t_{b,c}, F t_{b,c'} > ] ,
+ *   t_{b,c}[p*rg + q] = sum_{i,g} UA[i][p] W[i][g] M_{b,c}[i][g] UG[g][q] .
+ *   kfac_inf_cov        dense rows M (J as kfac_cov_job): X = UA^T (M o W), t = X UG, y = t F^T,
+ *                       then the per-entry weighted Gram of the raw rows minus the Gram of y
+ *   kfac_inf_cov_outer  Linear layers, M_{b,c} = abar_b delta_{b,c}^T, no row is formed:
+ *                       rho_b[g] = sum_i abar_b[i]^2 W[i][g] and H_b[p][g] = sum_i UA[i][p] abar_b[i] W[i][g]
+ *                       from ONE GEMM, t_{b,c}[p][q] = sum_g H_b[p][g] delta_{b,c}[g] UG[g][q], y = t F^T,
+ *                       then Delta_b diag(rho_b) Delta_b^T minus the Gram of y
+ * W and F are plain numbers (W >= 0): the calls know nothing of damping.  Guarantees: every
+ * reduction runs in a fixed order, the sums across segments, the difference of the two terms
+ * and the sum across jobs in fp64; no atomics; two calls give identical bits; every nc x nc
+ * block is bitwise symmetric; a sample's block depends on that sample only (chunking the
+ * samples changes no bit).  The diagonal is the difference of two non-negative sums and is
+ * NOT clamped: where the low-rank term cancels the diagonal one it may come out negative at
+ * rounding level.  At most 8 jobs and nc <= 32 per call; KFAC_EINVAL is returned before any
+ * launch, KFAC_EWORKSPACE when the workspace is smaller than the query's answer.          */
+typedef struct kfac_inf_cov_job {
+  const float* J; /* as kfac_cov_job */
+  int64_t ldJ;
+  int32_t nA, nG;
+  const float* UA; /* nA x ra, row-major */
+  int64_t ldA;
+  int32_t ra;
+  const float* UG; /* nG x rg */
+  int64_t ldG;
+  int32_t rg;
+  const float* W; /* nA*nG, element (i, g) at W[i*nG + g] */
+  int64_t ldW;    /* >= nA*nG */
+  const float* F; /* r x r, row-major, r = ra*rg, index p*rg + q */
+  int64_t ldF;
+} kfac_inf_cov_job;
+
+KFAC_API size_t kfac_inf_cov_workspace_bytes(const kfac_inf_cov_job* jobs, int njobs, int64_t nb, int nc);
+KFAC_API int kfac_inf_cov(const kfac_inf_cov_job* jobs, int njobs, int64_t nb, int nc, int accumulate,
+                          float* cov, void* workspace, size_t workspace_bytes, kfac_stream_t stream);
+
+typedef struct kfac_inf_cov_outer_job {
+  const float* a; /* as kfac_cov_outer_job */
+  int64_t lda;
+  int32_t cols, has_ones;
+  const float* D;
+  int64_t ldD;
+  int32_t nG, reserved;
+  const float* UA; /* nA x ra, nA = cols + has_ones */
+  int64_t ldA;
+  int32_t ra;
+  const float* UG; /* nG x rg */
+  int64_t ldG;
+  int32_t rg;
+  const float* W; /* as kfac_inf_cov_job */
+  int64_t ldW;
+  const float* F;
+  int64_t ldF;
+} kfac_inf_cov_outer_job;
+
+KFAC_API size_t kfac_inf_cov_outer_workspace_bytes(const kfac_inf_cov_outer_job* jobs, int njobs, int64_t nb,
+                                                   int nc);
+KFAC_API int kfac_inf_cov_outer(const kfac_inf_cov_outer_job* jobs, int njobs, int64_t nb, int nc,
+                                int accumulate, float* cov, void* workspace, size_t workspace_bytes,
+                                kfac_stream_t stream);
+
 /* -------------------------------------------------------- posterior samples
  * out_j = (LA_j Z_j LG_j^T)^T, shape (nG x nA): KFAC.sample, curvatures.py:400-405,
  * with Z (nA x nG row-major) supplied by the caller (torch.randn, the reference's
