@@ -281,6 +281,14 @@ SIGNATURES = {
     "kfac_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "kfac_version": (ctypes.c_char_p, []),
 }
+# the class-tiled weighted covariance calls: their capped siblings' job structs and arguments
+for _name, _job in (("kfac_kron_cov_full_tiled", CovFullJob), ("kfac_kron_cov_outer_full_tiled", CovOuterFullJob),
+                    ("kfac_kron_cov_sweep_tiled", CovSweepJob),
+                    ("kfac_kron_cov_outer_sweep_tiled", CovOuterSweepJob)):
+    SIGNATURES[_name + "_workspace_bytes"] = (ctypes.c_size_t, [ctypes.POINTER(_job), ctypes.c_int, c_i64,
+                                                                ctypes.c_int, ctypes.c_int])
+    SIGNATURES[_name] = (ctypes.c_int, [ctypes.POINTER(_job), ctypes.c_int, c_i64, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp])
 
 _lib = None
 _lock = threading.Lock()
@@ -821,6 +829,32 @@ def kron_cov_outer_full(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accu
     ws = workspace.get(out.device, need)
     check(L.kfac_kron_cov_outer_full(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws),
                                      ws.numel(), stream_handle(out.device)), "kfac_kron_cov_outer_full")
+
+
+def _weighted_tiled(name: str, struct):
+    """(workspace query, call) of the class-tiled weighted covariance call `name`: the capped
+    sibling's job struct and (nt, nb, nc, nc) output, nc not capped, <= 8 jobs, nt <= 64."""
+    def workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
+        return getattr(lib(), name + "_workspace_bytes")(as_array(struct, jobs), len(jobs), nb, nc, nt)
+
+    def call(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
+        L = lib()
+        arr = as_array(struct, jobs)
+        need = getattr(L, name + "_workspace_bytes")(arr, len(jobs), nb, nc, nt)
+        ws = workspace.get(out.device, need)
+        check(getattr(L, name)(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws), ws.numel(),
+                               stream_handle(out.device)), name)
+
+    return workspace_bytes, call
+
+
+kron_cov_full_tiled_workspace_bytes, kron_cov_full_tiled = _weighted_tiled("kfac_kron_cov_full_tiled", CovFullJob)
+kron_cov_outer_full_tiled_workspace_bytes, kron_cov_outer_full_tiled = _weighted_tiled(
+    "kfac_kron_cov_outer_full_tiled", CovOuterFullJob)
+kron_cov_sweep_tiled_workspace_bytes, kron_cov_sweep_tiled = _weighted_tiled("kfac_kron_cov_sweep_tiled",
+                                                                             CovSweepJob)
+kron_cov_outer_sweep_tiled_workspace_bytes, kron_cov_outer_sweep_tiled = _weighted_tiled(
+    "kfac_kron_cov_outer_sweep_tiled", CovOuterSweepJob)
 
 
 def inf_cov_workspace_bytes(jobs, nb: int, nc: int) -> int:

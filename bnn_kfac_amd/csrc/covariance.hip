@@ -302,10 +302,6 @@ static size_t sweep_t_bytes(const kfac_cov_sweep_job& j, int64_t rows) {
 static size_t sweep_partial_bytes(const kfac_cov_sweep_job& j, int64_t nb, int nc, int nt) {
   return align_up((size_t)(nb * sweep_nseg(j)) * nc * nc * nt * sizeof(float), 256);
 }
-static bool sweep_job_ok(const kfac_cov_sweep_job& q) {
-  return q.J && q.VA && q.VG && q.wA && q.wG && q.nA > 0 && q.nG > 0 && q.ldA >= q.nA &&
-         q.ldG >= q.nG && q.ldwA >= q.nA && q.ldwG >= q.nG && q.ldJ >= (int64_t)q.nA * q.nG;
-}
 
 extern "C" size_t kfac_kron_cov_sweep_workspace_bytes(const kfac_cov_sweep_job* jobs, int njobs,
                                                       int64_t nb, int nc, int nt) {

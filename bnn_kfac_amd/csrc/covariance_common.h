@@ -6,7 +6,8 @@
 // (covariance_joint.hip) take from both: the argument blocks of the apply / V launches, the
 // Abar^T panel, and the 64x64 Gram tile all three of their operands go through; the
 // class-tiled per-sample calls (covariance_tiled.hip) run that tile on one sample's rows; the
-// draw calls (covariance_draws.hip) start from the same apply / U / V launches.
+// class-tiled weighted calls (covariance_wtiled.hip) take the sweep / per-entry calls' job
+// checks and projection launches and the tiled calls' row and tile-pair counts; the draw calls (covariance_draws.hip) start from the same apply / U / V launches.
 #pragma once
 
 #include "kfac_common.h"
@@ -189,6 +190,12 @@ __device__ __forceinline__ void cov_wgram_segment(const float* Tb, int64_t K, in
   }
 }
 
+// OpDev has one pointer: the second operand of a product formed in a loader rides in sB.
+__device__ __forceinline__ int64_t aux_bits(const float* p) { return (int64_t)reinterpret_cast<intptr_t>(p); }
+__device__ __forceinline__ const float* aux_ptr(int64_t v) {
+  return reinterpret_cast<const float*>((intptr_t)v);
+}
+
 // ---- what the joint calls (covariance_joint.hip) share with the per-sample ones: the
 // argument blocks of the apply / V launches, the Abar^T panel, the job checks
 struct CovJobDev {
@@ -238,6 +245,15 @@ struct OuterArgs {
 };
 static_assert(sizeof(OuterArgs) <= 4096, "kernel argument block");
 
+// kfac_kron_cov_outer_full's R launch (covariance_full.hip)
+struct FullOuterArgs {
+  int ntau;
+  int r_begin[CMAXJ], r_end[CMAXJ];  // tasks of the R launch
+  const float* W[CMAXJ];
+  int64_t ldW[CMAXJ];
+  float* R[CMAXJ];                   // ntau x nb x nG
+};
+
 // kfac_cov_apply_u + kfac_cov_apply_t (covariance.hip) on a filled block: U, then T, for
 // all rows of every job; kfac_cov_outer_v (covariance_outer.hip): V = Delta K2.
 int cov_launch_apply(const CovArgs& args, hipStream_t s);
@@ -250,6 +266,13 @@ int cov_launch_outer_u(const OuterArgs& args, int64_t nn, hipStream_t s);
 // kfac_cov_sweep_reduce (covariance.hip) on a block whose njobs, nc, nb, accumulate, cov and
 // the jobs' partial (ntau x nb x nseg x nc*nc) / nseg are filled.
 int cov_launch_sweep_reduce(const CovArgs& args, int ntau, hipStream_t s);
+
+// kfac_cov_proj2 (P2T at OuterJobDev::norm, nn tasks: the row-norm launch's ranges) and
+// kfac_cov_full_r (R_t = P2T^T W_t, nr tasks) of covariance_full.hip, and kfac_cov_rownorm_w
+// (covariance_outer.hip: norm[tau][tile][b], nn tasks) on filled blocks.
+int cov_launch_proj2(const OuterArgs& args, int64_t nn, hipStream_t s);
+int cov_launch_full_r(const OuterArgs& args, const FullOuterArgs& fa, int64_t nr, hipStream_t s);
+int cov_launch_rownorm_w(const OuterArgs& args, const SweepArgs& sw, int64_t nn, hipStream_t s);
 
 constexpr int KFAC_SAMPLEROWS = 17;  // panel layout of Abar^T (internal to the outer routes)
 
@@ -313,6 +336,27 @@ static inline size_t outer_norm_bytes(const kfac_cov_outer_job& j, int64_t nb) {
 static inline bool outer_job_ok(const kfac_cov_outer_job& q) {
   return q.a && q.D && q.K1 && q.K2 && q.cols > 0 && q.nG > 0 && q.lda >= q.cols &&
          q.ldD >= q.nG && q.ld1 >= outer_nA(q) && q.ld2 >= q.nG;
+}
+
+// the job checks of the weighted calls (capped and class-tiled)
+static inline bool sweep_job_ok(const kfac_cov_sweep_job& q) {
+  return q.J && q.VA && q.VG && q.wA && q.wG && q.nA > 0 && q.nG > 0 && q.ldA >= q.nA &&
+         q.ldG >= q.nG && q.ldwA >= q.nA && q.ldwG >= q.nG && q.ldJ >= (int64_t)q.nA * q.nG;
+}
+static inline int64_t osweep_nA(const kfac_cov_outer_sweep_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
+static inline bool osweep_job_ok(const kfac_cov_outer_sweep_job& q) {
+  return q.a && q.D && q.VA && q.VG && q.wA && q.wG && q.cols > 0 && q.nG > 0 && q.lda >= q.cols &&
+         q.ldD >= q.nG && q.ldA >= osweep_nA(q) && q.ldG >= q.nG && q.ldwA >= osweep_nA(q) &&
+         q.ldwG >= q.nG;
+}
+static inline bool full_job_ok(const kfac_cov_full_job& q) {
+  return q.J && q.VA && q.VG && q.W && q.nA > 0 && q.nG > 0 && q.ldA >= q.nA && q.ldG >= q.nG &&
+         q.ldW >= (int64_t)q.nA * q.nG && q.ldJ >= (int64_t)q.nA * q.nG;
+}
+static inline int64_t ofull_nA(const kfac_cov_outer_full_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
+static inline bool ofull_job_ok(const kfac_cov_outer_full_job& q) {
+  return q.a && q.D && q.VA && q.VG && q.W && q.cols > 0 && q.nG > 0 && q.lda >= q.cols &&
+         q.ldD >= q.nG && q.ldA >= ofull_nA(q) && q.ldG >= q.nG && q.ldW >= ofull_nA(q) * q.nG;
 }
 
 // The apply part of a CovArgs block (jobs' operands, the U / T task ranges, nu, nt) for
@@ -379,6 +423,18 @@ static inline bool cov_fill_outer(const kfac_cov_outer_job* jobs, int njobs, int
 // per-sample covariance (kfac_kron_cov_tiled / kfac_kron_cov_outer_tiled)
 constexpr int JSEG = GSEG;          // K elements per joint-gram task: a function of K alone
 constexpr int JTILE2 = TILE * TILE; // floats per tile partial
+
+// tile pairs ti >= tj of an nc x nc block
+static inline int64_t tiled_npairs(int nc) {
+  const int64_t t = cdiv(nc, TILE);
+  return t * (t + 1) / 2;
+}
+// rows = nb*nc with 32-bit rows (the sibling calls' limit), or 0
+static inline int64_t tiled_rows(int64_t nb, int nc) {
+  const int64_t lim = (int64_t)1 << 31;
+  if (nb <= 0 || nc <= 0 || nb >= (lim - TILE) / nc) return 0;
+  return nb * nc;
+}
 
 // One 64x64 tile (ti >= tj) of X X^T over the K segment [k0, k1): X is rows x K with K
 // contiguous per row, part the fp32 64x64 partial (row-major, row = the tile-ti row).  The

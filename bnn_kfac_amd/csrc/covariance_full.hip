@@ -31,14 +31,6 @@
 
 namespace kfac {
 
-struct FullOuterArgs {
-  int ntau;
-  int r_begin[CMAXJ], r_end[CMAXJ];  // tasks of the R launch
-  const float* W[CMAXJ];
-  int64_t ldW[CMAXJ];
-  float* R[CMAXJ];                   // ntau x nb x nG
-};
-
 // Weighted Gram partials of the projected rows, per-entry weights: kfac_cov_sweep_gram
 // with sw.job[j].wG = W_j, ldwG = ldW_j (wA unused).
 __global__ __launch_bounds__(NTHREADS) void kfac_cov_full_gram(CovArgs args, SweepArgs sw) {
@@ -134,12 +126,7 @@ static size_t full_t_bytes(const kfac_cov_full_job& j, int64_t rows) {
 static size_t full_partial_bytes(const kfac_cov_full_job& j, int64_t nb, int nc, int nt) {
   return align_up((size_t)(nb * full_nseg(j)) * nc * nc * nt * sizeof(float), 256);
 }
-static bool full_job_ok(const kfac_cov_full_job& q) {
-  return q.J && q.VA && q.VG && q.W && q.nA > 0 && q.nG > 0 && q.ldA >= q.nA && q.ldG >= q.nG &&
-         q.ldW >= (int64_t)q.nA * q.nG && q.ldJ >= (int64_t)q.nA * q.nG;
-}
 
-static int64_t ofull_nA(const kfac_cov_outer_full_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
 static int64_t ofull_nseg(const kfac_cov_outer_full_job& j) { return cdiv(j.nG, WSEG); }
 static size_t ofull_p2_bytes(const kfac_cov_outer_full_job& j, int64_t nb) {
   return align_up((size_t)(ofull_nA(j) * nb) * sizeof(float), 256);
@@ -153,9 +140,18 @@ static size_t ofull_v_bytes(const kfac_cov_outer_full_job& j, int64_t rows) {
 static size_t ofull_partial_bytes(const kfac_cov_outer_full_job& j, int64_t nb, int nc, int nt) {
   return align_up((size_t)(nb * ofull_nseg(j)) * nc * nc * nt * sizeof(float), 256);
 }
-static bool ofull_job_ok(const kfac_cov_outer_full_job& q) {
-  return q.a && q.D && q.VA && q.VG && q.W && q.cols > 0 && q.nG > 0 && q.lda >= q.cols &&
-         q.ldD >= q.nG && q.ldA >= ofull_nA(q) && q.ldG >= q.nG && q.ldW >= ofull_nA(q) * q.nG;
+
+// The projection launches alone (kfac_kron_cov_outer_full_tiled forms its own Grams from R and V).
+int cov_launch_proj2(const OuterArgs& args, int64_t nn, hipStream_t s) {
+  hipLaunchKernelGGL(kfac_cov_proj2, dim3((unsigned)nn), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}
+
+int cov_launch_full_r(const OuterArgs& args, const FullOuterArgs& fa, int64_t nr, hipStream_t s) {
+  hipLaunchKernelGGL(kfac_cov_full_r, dim3((unsigned)nr), dim3(NTHREADS), 0, s, args, fa);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
 }
 }  // namespace kfac
 

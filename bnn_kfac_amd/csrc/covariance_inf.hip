@@ -37,12 +37,6 @@ constexpr int KFAC_INF_HD = 21;  // (k = g, m = (b, c, p)) = HR[b][p][g] * D[b*n
 constexpr int KFAC_INF_WJ = 22;  // (k = i, j = (row, g)) = W[i][g] * J[row][i*nG + g]
 constexpr int ISEG = WSEG;       // elements of r per kfac_inf_gram2 workgroup (multiple of BK)
 
-// OpDev has one pointer: the second operand of a product formed in a loader rides in sB.
-__device__ __forceinline__ int64_t aux_bits(const float* p) { return (int64_t)reinterpret_cast<intptr_t>(p); }
-__device__ __forceinline__ const float* aux_ptr(int64_t v) {
-  return reinterpret_cast<const float*>((intptr_t)v);
-}
-
 // a (nb x kcols, stride lda), UA (nA x ra, stride ldA); columns m < ncols = nb*(ra + 1)
 __device__ __forceinline__ OpDev inf_au_op(const float* a, int kcols, int ones, int64_t lda, const float* UA,
                                            int64_t ldA, int ra, int ncols) {

@@ -231,6 +231,13 @@ int cov_launch_rownorm(const OuterArgs& args, int64_t nn, hipStream_t s) {
   return KFAC_OK;
 }
 
+// The weighted row-norm launch alone (kfac_kron_cov_outer_sweep_tiled forms its own Grams).
+int cov_launch_rownorm_w(const OuterArgs& args, const SweepArgs& sw, int64_t nn, hipStream_t s) {
+  hipLaunchKernelGGL(kfac_cov_rownorm_w, dim3((unsigned)nn), dim3(NTHREADS), 0, s, args, sw);
+  KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}
+
 // The V launch alone (kfac_kron_cov_outer_joint forms its own Grams from U and V).
 int cov_launch_outer_v(const OuterArgs& args, int64_t nv, hipStream_t s) {
   hipLaunchKernelGGL(kfac_cov_outer_v, dim3((unsigned)nv), dim3(NTHREADS), 0, s, args);
@@ -309,7 +316,6 @@ extern "C" int kfac_kron_cov_outer(const kfac_cov_outer_job* jobs, int njobs, in
 
 // ------------------------------------------------------------------ damping sweep
 namespace kfac {
-static int64_t osweep_nA(const kfac_cov_outer_sweep_job& j) { return (int64_t)j.cols + (j.has_ones != 0); }
 static int64_t osweep_nseg(const kfac_cov_outer_sweep_job& j) { return cdiv(j.nG, WSEG); }
 static size_t osweep_norm_bytes(const kfac_cov_outer_sweep_job& j, int64_t nb, int nt) {
   return align_up((size_t)(cdiv(osweep_nA(j), TILE) * nb) * nt * sizeof(float), 256);
@@ -319,11 +325,6 @@ static size_t osweep_v_bytes(const kfac_cov_outer_sweep_job& j, int64_t rows) {
 }
 static size_t osweep_partial_bytes(const kfac_cov_outer_sweep_job& j, int64_t nb, int nc, int nt) {
   return align_up((size_t)(nb * osweep_nseg(j)) * nc * nc * nt * sizeof(float), 256);
-}
-static bool osweep_job_ok(const kfac_cov_outer_sweep_job& q) {
-  return q.a && q.D && q.VA && q.VG && q.wA && q.wG && q.cols > 0 && q.nG > 0 && q.lda >= q.cols &&
-         q.ldD >= q.nG && q.ldA >= osweep_nA(q) && q.ldG >= q.nG && q.ldwA >= osweep_nA(q) &&
-         q.ldwG >= q.nG;
 }
 }  // namespace kfac
 

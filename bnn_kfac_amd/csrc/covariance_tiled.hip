@@ -109,18 +109,8 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_outer_tiled_reduce(TiledArg
   tiled_reduce_tile<true>(args);
 }
 
-static int64_t tiled_npairs(int nc) {
-  const int64_t t = cdiv(nc, TILE);
-  return t * (t + 1) / 2;
-}
 static size_t tiled_partial_bytes(int64_t nb, int nc, int64_t K) {
   return align_up((size_t)(nb * tiled_npairs(nc) * cdiv(K, JSEG)) * JTILE2 * sizeof(float), 256);
-}
-// rows = nb*nc with 32-bit rows (the sibling calls' limit), or 0
-static int64_t tiled_rows(int64_t nb, int nc) {
-  const int64_t lim = (int64_t)1 << 31;
-  if (nb <= 0 || nc <= 0 || nb >= (lim - TILE) / nc) return 0;
-  return nb * nc;
 }
 
 // job i of the Gram launch: nb samples x segments x tile pairs; false: the tasks (and with

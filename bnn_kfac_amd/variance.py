@@ -818,17 +818,9 @@ def _run_sweep(build, workspace_bytes, call, njobs, nb, nc, nt, device, max_work
     return out
 
 
-def kron_covariance_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
-                          max_workspace_bytes: int = 1 << 30) -> Tensor:
-    """kron_covariance over a grid of nt weightings in the factors' eigenbasis:
-    cov[t, b, c, c'] = sum_l sum_{i,g} wA_l[t, i] wG_l[t, g] Y_l[b, c][i, g] Y_l[b, c'][i, g],
-    Y_l[b, c] = VA_l^T M_l[b, c] VG_l projected once for all t.
-
-    terms: [(J_l, VA_l, VG_l, wA_l, wG_l)], J as kron_covariance takes it, VA (nA x nA) /
-    VG (nG x nG) eigenvectors as columns, wA (nt, nA) / wG (nt, nG) non-negative weights
-    (damping_weights).  Returns (nt, nb, nc, nc) fp32; per grid point kron_covariance's
-    guarantees hold, and slice t has the bits of the call with row t's weights alone.
-    """
+def _sweep_dense(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
+    """kron_covariance_sweep / kron_covariance_sweep_tiled: the terms parsed and checked, then
+    `call` through _run_sweep; `max_classes` None: no cap on nc."""
     if not terms:
         raise ValueError("no terms")
     keep, jobs = [], []
@@ -847,8 +839,8 @@ def kron_covariance_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, 
             raise ValueError("all terms need the same (nb, nc)")
         if wAc.shape[0] != nt or wGc.shape[0] != nt or nt == 0:
             raise ValueError("all weights need the same number nt >= 1 of rows")
-        if nc > MAX_COV_CLASSES:
-            raise ValueError(f"kron_covariance_sweep handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        if max_classes is not None and nc > max_classes:
+            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
         keep.extend([J3, VAc, VGc, wAc, wGc])
         jobs.append((J3.data_ptr(), ld, nA, nG, VAc.data_ptr(), ldA, VGc.data_ptr(), ldG,
                      wAc.data_ptr(), ldwA, wGc.data_ptr(), ldwG))
@@ -858,21 +850,38 @@ def kron_covariance_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, 
         return N.CovSweepJob(j[0] + 4 * b0 * nc * j[1], *j[1:8], j[8] + 4 * t0 * j[9], j[9],
                              j[10] + 4 * t0 * j[11], j[11])
 
-    return _run_sweep(build, N.kron_cov_sweep_workspace_bytes, N.kron_cov_sweep, len(jobs), nb, nc, nt,
-                      keep[0].device, max_workspace_bytes)
+    return _run_sweep(build, workspace_bytes, call, len(jobs), nb, nc, nt, keep[0].device, max_workspace_bytes)
 
 
-def kron_covariance_outer_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]],
-                                max_workspace_bytes: int = 1 << 30) -> Tensor:
-    """kron_covariance_outer over a grid of nt weightings in the factors' eigenbasis:
-    cov[t, b] = sum_l (sum_i wA_l[t, i] p_l[b][i]^2) Q_l[b] diag(wG_l[t]) Q_l[b]^T with
-    p_l[b] = VA_l^T [a_l[b] | 1] and Q_l[b] = D_l[b] VG_l projected once for all t.
+def kron_covariance_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
+                          max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance over a grid of nt weightings in the factors' eigenbasis:
+    cov[t, b, c, c'] = sum_l sum_{i,g} wA_l[t, i] wG_l[t, g] Y_l[b, c][i, g] Y_l[b, c'][i, g],
+    Y_l[b, c] = VA_l^T M_l[b, c] VG_l projected once for all t.
 
-    terms: [(a_l, D_l, VA_l, VG_l, wA_l, wG_l)], a and D as kron_covariance_outer takes them,
-    VA (nA x nA, nA = cols + 1 with the implicit ones column, or cols), VG (nG x nG), wA
-    (nt, nA), wG (nt, nG).  Returns (nt, nb, nc, nc) fp32 with kron_covariance_sweep's
-    guarantees.
+    terms: [(J_l, VA_l, VG_l, wA_l, wG_l)], J as kron_covariance takes it, VA (nA x nA) /
+    VG (nG x nG) eigenvectors as columns, wA (nt, nA) / wG (nt, nG) non-negative weights
+    (damping_weights).  Returns (nt, nb, nc, nc) fp32; per grid point kron_covariance's
+    guarantees hold, and slice t has the bits of the call with row t's weights alone.
     """
+    return _sweep_dense(terms, "kron_covariance_sweep", MAX_COV_CLASSES, N.kron_cov_sweep_workspace_bytes,
+                        N.kron_cov_sweep, max_workspace_bytes)
+
+
+def kron_covariance_sweep_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
+                                max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_sweep for any number of outputs: the same terms, the same
+    (nt, nb, nc, nc) fp32 result, nc not capped (kfac_kron_cov_sweep_tiled: a sample's block in
+    64x64 class tiles, the weights folded into one operand as it is loaded).  The guarantees
+    are kron_covariance_sweep's; with every weight 1 slice t has the bits of
+    kron_covariance_tiled(lower=False) on the same rows; against kron_covariance_sweep
+    (nc <= 32, another summation order) it agrees to fp32 rounding."""
+    return _sweep_dense(terms, "kron_covariance_sweep_tiled", None, N.kron_cov_sweep_tiled_workspace_bytes,
+                        N.kron_cov_sweep_tiled, max_workspace_bytes)
+
+
+def _sweep_outer(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
+    """kron_covariance_outer_sweep / kron_covariance_outer_sweep_tiled: as _sweep_dense."""
     if not terms:
         raise ValueError("no terms")
     keep, jobs = [], []
@@ -899,9 +908,8 @@ def kron_covariance_outer_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Te
             raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
         if wAc.shape[0] != nt or wGc.shape[0] != nt or nt == 0:
             raise ValueError("all weights need the same number nt >= 1 of rows")
-        if nc > MAX_COV_CLASSES:
-            raise ValueError(f"kron_covariance_outer_sweep handles at most {MAX_COV_CLASSES} outputs, "
-                             f"got {nc}")
+        if max_classes is not None and nc > max_classes:
+            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
         if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols):
             a2 = a2.contiguous()
         lda = a2.stride(0) if nb > 1 else cols
@@ -916,8 +924,40 @@ def kron_covariance_outer_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Te
         return N.CovOuterSweepJob(j[0] + 4 * b0 * j[1], j[1], j[2], j[3], j[4] + 4 * b0 * nc * j[5],
                                   *j[5:12], j[12] + 4 * t0 * j[13], j[13], j[14] + 4 * t0 * j[15], j[15])
 
-    return _run_sweep(build, N.kron_cov_outer_sweep_workspace_bytes, N.kron_cov_outer_sweep, len(jobs),
-                      nb, nc, nt, keep[0].device, max_workspace_bytes)
+    return _run_sweep(build, workspace_bytes, call, len(jobs), nb, nc, nt, keep[0].device, max_workspace_bytes)
+
+
+def kron_covariance_outer_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]],
+                                max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_outer over a grid of nt weightings in the factors' eigenbasis:
+    cov[t, b] = sum_l (sum_i wA_l[t, i] p_l[b][i]^2) Q_l[b] diag(wG_l[t]) Q_l[b]^T with
+    p_l[b] = VA_l^T [a_l[b] | 1] and Q_l[b] = D_l[b] VG_l projected once for all t.
+
+    terms: [(a_l, D_l, VA_l, VG_l, wA_l, wG_l)], a and D as kron_covariance_outer takes them,
+    VA (nA x nA, nA = cols + 1 with the implicit ones column, or cols), VG (nG x nG), wA
+    (nt, nA), wG (nt, nG).  Returns (nt, nb, nc, nc) fp32 with kron_covariance_sweep's
+    guarantees.
+    """
+    return _sweep_outer(terms, "kron_covariance_outer_sweep", MAX_COV_CLASSES,
+                        N.kron_cov_outer_sweep_workspace_bytes, N.kron_cov_outer_sweep, max_workspace_bytes)
+
+
+def kron_covariance_outer_sweep_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]],
+                                      max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_outer_sweep for any number of outputs: the same terms, the same
+    (nt, nb, nc, nc) fp32 result, nc not capped (kfac_kron_cov_outer_sweep_tiled).  The
+    guarantees are kron_covariance_sweep's; against kron_covariance_outer_sweep (nc <= 32,
+    another summation order) it agrees to fp32 rounding."""
+    return _sweep_outer(terms, "kron_covariance_outer_sweep_tiled", None,
+                        N.kron_cov_outer_sweep_tiled_workspace_bytes, N.kron_cov_outer_sweep_tiled,
+                        max_workspace_bytes)
+
+
+def _sweep_calls(nc: int):
+    """(dense, outer) damping-sweep covariance calls for nc outputs, as _per_sample_calls."""
+    if nc > MAX_COV_CLASSES:
+        return kron_covariance_sweep_tiled, kron_covariance_outer_sweep_tiled
+    return kron_covariance_sweep, kron_covariance_outer_sweep
 
 
 def glm_predictive_sweep(kfac, x: Tensor, dampings, layers: Iterable = None, chunk: int = 64,
@@ -951,7 +991,8 @@ def glm_predictive_sweep(kfac, x: Tensor, dampings, layers: Iterable = None, chu
         xc = x[c0:c0 + chunk]
         if jacobians == "dense":
             f, Js = output_jacobians(model, layers, xc)
-            cov = kron_covariance_sweep([(J, *basis[layer]) for layer, J in zip(layers, Js)])
+            cov_dense, _ = _sweep_calls(f.shape[1])
+            cov = cov_dense([(J, *basis[layer]) for layer, J in zip(layers, Js)])
         else:
             f, io = layer_io_jacobians(model, layers, xc)
             outer, dense = [], []
@@ -965,9 +1006,10 @@ def glm_predictive_sweep(kfac, x: Tensor, dampings, layers: Iterable = None, chu
                 else:
                     raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
                                      f"{layer.__class__.__name__}")
-            cov = kron_covariance_outer_sweep(outer) if outer else None
+            cov_dense, cov_outer = _sweep_calls(f.shape[1])
+            cov = cov_outer(outer) if outer else None
             if dense:
-                conv = kron_covariance_sweep(dense)
+                conv = cov_dense(dense)
                 cov = conv if cov is None else cov + conv
         logits.append(f)
         covs.append(cov)
@@ -1029,18 +1071,10 @@ def _full_weights(W: Tensor):
     return W, (W.stride(0) if nt > 1 else nA * nG)
 
 
-def kron_covariance_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]],
-                         max_workspace_bytes: int = 1 << 30) -> Tensor:
-    """kron_covariance_sweep with a weight per eigenbasis entry instead of a rank-one pair:
-    cov[t, b, c, c'] = sum_l sum_{i,g} W_l[t, i, g] Y_l[b, c][i, g] Y_l[b, c'][i, g],
-    Y_l[b, c] = VA_l^T M_l[b, c] VG_l projected once for all t.
-
-    terms: [(J_l, VA_l, VG_l, W_l)], J, VA, VG as kron_covariance_sweep takes them, W
-    (nt, nA, nG) or (nA, nG) non-negative (efb_weights).  Returns (nt, nb, nc, nc) fp32 with
-    kron_covariance_sweep's guarantees: bitwise symmetric blocks, a sample's block depends on
-    that sample only, slice t has the bits of the call with W[t] alone.  Shapes are checked
-    (ValueError) before anything touches the device.
-    """
+def _full_dense(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
+    """kron_covariance_full / kron_covariance_full_tiled: the terms parsed and checked (shapes
+    before anything touches the device), then `call` through _run_sweep; `max_classes` None:
+    no cap on nc."""
     if not terms:
         raise ValueError("no terms")
     parsed = []
@@ -1054,8 +1088,8 @@ def kron_covariance_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]],
             raise ValueError("all terms need the same (nb, nc)")
         if W3.shape[0] != nt or nt == 0:
             raise ValueError("all weights need the same number nt >= 1 of matrices")
-        if nc > MAX_COV_CLASSES:
-            raise ValueError(f"kron_covariance_full handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        if max_classes is not None and nc > max_classes:
+            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
         parsed.append((J3, ld, nA, nG, VA, VG, W3))
     keep, jobs = [], []
     for J3, ld, nA, nG, VA, VG, W3 in parsed:
@@ -1070,20 +1104,39 @@ def kron_covariance_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]],
         j = jobs[i]
         return N.CovFullJob(j[0] + 4 * b0 * nc * j[1], *j[1:8], j[8] + 4 * t0 * j[9], j[9])
 
-    return _run_sweep(build, N.kron_cov_full_workspace_bytes, N.kron_cov_full, len(jobs), nb, nc, nt,
-                      keep[0].device, max_workspace_bytes)
+    return _run_sweep(build, workspace_bytes, call, len(jobs), nb, nc, nt, keep[0].device, max_workspace_bytes)
 
 
-def kron_covariance_outer_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
-                               max_workspace_bytes: int = 1 << 30) -> Tensor:
-    """kron_covariance_full for Linear layers without their Jacobian rows:
-    cov[t, b] = sum_l Q_l[b] diag(r_l[t, b]) Q_l[b]^T, r_l[t, b][g] = sum_i p_l[b][i]^2 W_l[t, i, g],
-    with p_l[b] = VA_l^T [a_l[b] | 1] and Q_l[b] = D_l[b] VG_l projected once for all t.
+def kron_covariance_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]],
+                         max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_sweep with a weight per eigenbasis entry instead of a rank-one pair:
+    cov[t, b, c, c'] = sum_l sum_{i,g} W_l[t, i, g] Y_l[b, c][i, g] Y_l[b, c'][i, g],
+    Y_l[b, c] = VA_l^T M_l[b, c] VG_l projected once for all t.
 
-    terms: [(a_l, D_l, VA_l, VG_l, W_l)], a, D, VA, VG as kron_covariance_outer_sweep takes
-    them, W (nt, nA, nG) or (nA, nG).  Returns (nt, nb, nc, nc) fp32 with
-    kron_covariance_full's guarantees.
+    terms: [(J_l, VA_l, VG_l, W_l)], J, VA, VG as kron_covariance_sweep takes them, W
+    (nt, nA, nG) or (nA, nG) non-negative (efb_weights).  Returns (nt, nb, nc, nc) fp32 with
+    kron_covariance_sweep's guarantees: bitwise symmetric blocks, a sample's block depends on
+    that sample only, slice t has the bits of the call with W[t] alone.  Shapes are checked
+    (ValueError) before anything touches the device.
     """
+    return _full_dense(terms, "kron_covariance_full", MAX_COV_CLASSES, N.kron_cov_full_workspace_bytes,
+                       N.kron_cov_full, max_workspace_bytes)
+
+
+def kron_covariance_full_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]],
+                               max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_full for any number of outputs: the same terms, the same
+    (nt, nb, nc, nc) fp32 result, nc not capped (kfac_kron_cov_full_tiled: a sample's block in
+    64x64 class tiles, the weights folded into one operand as it is loaded).  The guarantees
+    are kron_covariance_full's; with every weight 1 slice t has the bits of
+    kron_covariance_tiled(lower=False) on the same rows; against kron_covariance_full
+    (nc <= 32, another summation order) it agrees to fp32 rounding."""
+    return _full_dense(terms, "kron_covariance_full_tiled", None, N.kron_cov_full_tiled_workspace_bytes,
+                       N.kron_cov_full_tiled, max_workspace_bytes)
+
+
+def _full_outer(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
+    """kron_covariance_outer_full / kron_covariance_outer_full_tiled: as _full_dense."""
     if not terms:
         raise ValueError("no terms")
     parsed = []
@@ -1106,9 +1159,8 @@ def kron_covariance_outer_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Ten
             raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
         if W3.shape[0] != nt or nt == 0:
             raise ValueError("all weights need the same number nt >= 1 of matrices")
-        if nc > MAX_COV_CLASSES:
-            raise ValueError(f"kron_covariance_outer_full handles at most {MAX_COV_CLASSES} outputs, "
-                             f"got {nc}")
+        if max_classes is not None and nc > max_classes:
+            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
         parsed.append((a2, cols, D3, ldD, nA, nG, VA, VG, W3))
     keep, jobs = [], []
     for a2, cols, D3, ldD, nA, nG, VA, VG, W3 in parsed:
@@ -1129,8 +1181,39 @@ def kron_covariance_outer_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Ten
         return N.CovOuterFullJob(j[0] + 4 * b0 * j[1], j[1], j[2], j[3], j[4] + 4 * b0 * nc * j[5],
                                  *j[5:12], j[12] + 4 * t0 * j[13], j[13])
 
-    return _run_sweep(build, N.kron_cov_outer_full_workspace_bytes, N.kron_cov_outer_full, len(jobs),
-                      nb, nc, nt, keep[0].device, max_workspace_bytes)
+    return _run_sweep(build, workspace_bytes, call, len(jobs), nb, nc, nt, keep[0].device, max_workspace_bytes)
+
+
+def kron_covariance_outer_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
+                               max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_full for Linear layers without their Jacobian rows:
+    cov[t, b] = sum_l Q_l[b] diag(r_l[t, b]) Q_l[b]^T, r_l[t, b][g] = sum_i p_l[b][i]^2 W_l[t, i, g],
+    with p_l[b] = VA_l^T [a_l[b] | 1] and Q_l[b] = D_l[b] VG_l projected once for all t.
+
+    terms: [(a_l, D_l, VA_l, VG_l, W_l)], a, D, VA, VG as kron_covariance_outer_sweep takes
+    them, W (nt, nA, nG) or (nA, nG).  Returns (nt, nb, nc, nc) fp32 with
+    kron_covariance_full's guarantees.
+    """
+    return _full_outer(terms, "kron_covariance_outer_full", MAX_COV_CLASSES,
+                       N.kron_cov_outer_full_workspace_bytes, N.kron_cov_outer_full, max_workspace_bytes)
+
+
+def kron_covariance_outer_full_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
+                                     max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_outer_full for any number of outputs: the same terms, the same
+    (nt, nb, nc, nc) fp32 result, nc not capped (kfac_kron_cov_outer_full_tiled).  The
+    guarantees are kron_covariance_full's; against kron_covariance_outer_full (nc <= 32,
+    another summation order) it agrees to fp32 rounding."""
+    return _full_outer(terms, "kron_covariance_outer_full_tiled", None,
+                       N.kron_cov_outer_full_tiled_workspace_bytes, N.kron_cov_outer_full_tiled,
+                       max_workspace_bytes)
+
+
+def _full_calls(nc: int):
+    """(dense, outer) per-entry-weight covariance calls for nc outputs, as _per_sample_calls."""
+    if nc > MAX_COV_CLASSES:
+        return kron_covariance_full_tiled, kron_covariance_outer_full_tiled
+    return kron_covariance_full, kron_covariance_outer_full
 
 
 def efb_weights(lam: Tensor, dampings: Sequence[Tuple[float, float]]) -> Tensor:
@@ -1159,7 +1242,8 @@ def _efb_chunk(model, layers, basis, x, jacobians):
     """(logits, cov (nt, n, nc, nc)) of one chunk; basis[layer] = (VA, VG, W (nt, nA, nG))."""
     if jacobians == "dense":
         f, Js = output_jacobians(model, layers, x)
-        return f, kron_covariance_full([(J, *basis[layer]) for layer, J in zip(layers, Js)])
+        cov_dense, _ = _full_calls(f.shape[1])
+        return f, cov_dense([(J, *basis[layer]) for layer, J in zip(layers, Js)])
     f, io = layer_io_jacobians(model, layers, x)
     outer, dense = [], []
     for layer, (a, D) in zip(layers, io):
@@ -1172,9 +1256,10 @@ def _efb_chunk(model, layers, basis, x, jacobians):
         else:
             raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
                              f"{layer.__class__.__name__}")
-    cov = kron_covariance_outer_full(outer) if outer else None
+    cov_dense, cov_outer = _full_calls(f.shape[1])
+    cov = cov_outer(outer) if outer else None
     if dense:
-        conv = kron_covariance_full(dense)
+        conv = cov_dense(dense)
         cov = conv if cov is None else cov + conv
     return f, cov
 

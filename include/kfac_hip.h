@@ -583,6 +583,60 @@ KFAC_API int kfac_kron_cov_outer_full(const kfac_cov_outer_full_job* jobs, int n
                                       int nt, int accumulate, float* cov, void* workspace,
                                       size_t workspace_bytes, kfac_stream_t stream);
 
+/* ------- GLM predictive covariance over a damping grid / with per-entry weights, any number of outputs
+ * The four weighted calls above with the classes tiled instead of capped: the same job
+ * structs, the same cov (nt x nb x nc x nc contiguous), nc >= 1 with no cap, 1 <= nt <= 64.
+ * The projections are the capped calls' own launches over all nb*nc rows at once; a sample's
+ * block is then cut into 64x64 class tiles and every tile pair ti >= tj is one weighted Gram
+ * tile of that sample's projected rows X_b (nc x K),
+ *   part[r][r'] = sum_k X_b[r][k] * (w_t[k] * X_b[r'][k]) ,
+ * the weight folded into one operand as it is loaded (no product is stored):
+ *   kfac_kron_cov_full_tiled         X = Y (K = nA*nG), w_t[k] = W_t[k]
+ *   kfac_kron_cov_sweep_tiled        X = Y (K = nA*nG), w_t[k] = wA_t[k / nG] * wG_t[k % nG]
+ *   kfac_kron_cov_outer_full_tiled   X = Q_b (K = nG),  w_t = r_{t,b}
+ *   kfac_kron_cov_outer_sweep_tiled  X = Q_b (K = nG),  w_t = wG_t, the block times
+ *                                    s_{t,b} = sum_i wA_t[i] p_b[i]^2
+ * K is cut into 2048-long segments that depend on K alone; a tile is summed over a segment in
+ * fp32 (MFMA, exact products, one k-ordered chain from 0 per element), the partials over
+ * segments in segment order, (outer sweep: times s_{t,b}, summed over its 64-column tiles in
+ * tile order,) over jobs in job order, all in fp64, without atomics.  Hence: two calls give
+ * identical bits; every block is bitwise symmetric (the lower triangle is computed and
+ * mirrored); a sample's block depends on that sample only, so chunking the samples changes no
+ * bit; slice t has the bits of the nt = 1 call with grid point t's weights (one grid point per
+ * Gram task); and with every weight equal to 1 kfac_kron_cov_full_tiled and
+ * kfac_kron_cov_sweep_tiled give, on every slice, the bits of kfac_kron_cov_tiled with
+ * K1 = VA, K2 = VG dense (one tile body, segmentation and reduce order; x * 1 is exact).
+ * Against the capped calls (nc <= 32 is valid here: one tile pair) the summation order
+ * differs: agreement to fp32 rounding.  accumulate: cov += the sum, else cov = it.
+ * At most 8 jobs per call; nb*nc, rows*nG, rows*nA as in the calls above, and the Gram
+ * launch's task count (nb x segments x nt x tile pairs, summed over the jobs) must fit 31
+ * bits.  KFAC_EINVAL is returned before any launch, KFAC_EWORKSPACE when the workspace is
+ * smaller than the query's answer.  Workspace per job, every part rounded up to 256 bytes,
+ * P = nt * nb * ceil(K/2048) * t(t+1)/2 partials of 64x64 floats, t = ceil(nc/64):
+ *   full_tiled, sweep_tiled   U and T (nb*nc*nA*nG floats each), P with K = nA*nG
+ *   outer_full_tiled          P2T (nA*nb), R (nt*nb*nG), V (nb*nc*nG), P with K = nG
+ *   outer_sweep_tiled         the row-norm partials (nt*ceil(nA/64)*nb), V, P with K = nG */
+KFAC_API size_t kfac_kron_cov_full_tiled_workspace_bytes(const kfac_cov_full_job* jobs, int njobs,
+                                                         int64_t nb, int nc, int nt);
+KFAC_API int kfac_kron_cov_full_tiled(const kfac_cov_full_job* jobs, int njobs, int64_t nb, int nc, int nt,
+                                      int accumulate, float* cov, void* workspace, size_t workspace_bytes,
+                                      kfac_stream_t stream);
+KFAC_API size_t kfac_kron_cov_outer_full_tiled_workspace_bytes(const kfac_cov_outer_full_job* jobs,
+                                                               int njobs, int64_t nb, int nc, int nt);
+KFAC_API int kfac_kron_cov_outer_full_tiled(const kfac_cov_outer_full_job* jobs, int njobs, int64_t nb,
+                                            int nc, int nt, int accumulate, float* cov, void* workspace,
+                                            size_t workspace_bytes, kfac_stream_t stream);
+KFAC_API size_t kfac_kron_cov_sweep_tiled_workspace_bytes(const kfac_cov_sweep_job* jobs, int njobs,
+                                                          int64_t nb, int nc, int nt);
+KFAC_API int kfac_kron_cov_sweep_tiled(const kfac_cov_sweep_job* jobs, int njobs, int64_t nb, int nc,
+                                       int nt, int accumulate, float* cov, void* workspace,
+                                       size_t workspace_bytes, kfac_stream_t stream);
+KFAC_API size_t kfac_kron_cov_outer_sweep_tiled_workspace_bytes(const kfac_cov_outer_sweep_job* jobs,
+                                                                int njobs, int64_t nb, int nc, int nt);
+KFAC_API int kfac_kron_cov_outer_sweep_tiled(const kfac_cov_outer_sweep_job* jobs, int njobs, int64_t nb,
+                                             int nc, int nt, int accumulate, float* cov, void* workspace,
+                                             size_t workspace_bytes, kfac_stream_t stream);
+
 /* ------------------- GLM predictive covariance under the INF posterior
  * INF (low-rank EFB plus a diagonal correction) is Gaussian with precision
  *   P = s (U Lambda U^T + D+) + n I ,  U = kron(UA, UG)  (nA*nG x r, r = ra*rg).
