@@ -161,6 +161,8 @@ SIGNATURES = {
     "kfac_factor_route": (ctypes.c_int, [ctypes.POINTER(FactorJob), ctypes.c_int, ctypes.POINTER(c_i32)]),
     "kfac_factor_flush": (ctypes.c_int, [ctypes.POINTER(FactorJob), ctypes.c_int, c_vp]),
     "kfac_x3_unit_table": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_i32), ctypes.c_int]),
+    "kfac_x3_task_decode": (ctypes.c_int, [ctypes.POINTER(c_i32), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.POINTER(c_i32)]),
     "kfac_syrk_linear": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, ctypes.c_int, c_f32, c_f32,
                                         c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
     "kfac_syrk_conv": (ctypes.c_int, [c_vp, c_i64] + [ctypes.c_int] * 10 + [c_f32, c_f32, c_vp,

@@ -406,6 +406,22 @@ static int prepare_group(const kfac_factor_job* jobs, int njobs, const Route& ro
     tasks += plans[i].tasks;
     args.task_end[i] = tasks;
   }
+  // kfac_factor_tiles_x3 with every job at the same K-splits (the planner's one chunk
+  // length, or the callers' acc_splits): split-major across the whole launch, the task
+  // ranges counted in units per split (x3_task_decode)
+  if (route.family == KFAC_PROF_FACTOR_X3) {
+    bool same = true;
+    for (int i = 1; i < njobs; ++i) same &= args.job[i].splits == args.job[0].splits;
+    if (same && args.job[0].splits > 0) {
+      args.split_major = 2;
+      int units = 0;
+      for (int i = 0; i < njobs; ++i) {
+        args.job[i].task_begin = units;
+        units += args.job[i].x3units;
+        args.task_end[i] = units;
+      }
+    }
+  }
   g.tasks = tasks;
   g.rtiles = rtiles;
   return off > ws_bytes ? KFAC_EWORKSPACE : KFAC_OK;

@@ -49,7 +49,10 @@ struct FactorJobDev {
 struct FactorArgs {
   const float* segs[KSEG];  // batch bases of the multi-batch jobs (kernel arguments: no copy)
   int njobs;
-  int split_major;  // LDS-DMA path task order: 1 split-major, 0 tile-major (KFAC_SYRK_ORDER)
+  // task order: 1 split-major within each job, 0 tile-major (KFAC_SYRK_ORDER); 2
+  // (kfac_factor_tiles_x3 only, every job at job[0].splits K-splits): split-major across
+  // the whole launch (x3_task_decode)
+  int split_major;
   int task_end[MAXJ];
   int tile_end[MAXJ];
   FactorJobDev job[MAXJ];
@@ -108,9 +111,15 @@ __device__ __forceinline__ void put_partials(const FactorJobDev& J, int nb, cons
 // `seg` (s = seg * sps + k / BK), so a multi-batch job reads each batch in place.
 // `segs` = FactorArgs::segs (kernel-argument memory; never null: a conditional
 // null pointer here makes the compiler copy the whole argument block to scratch).
+// Both candidates are loaded and the VALUES selected (a single-batch job reads segs[0],
+// some job's base or null, and drops it): written as one conditional expression this is
+// a select of two argument-block addresses, which -- see seg_rows -- can cost that copy
+// too (kfac_factor_tiles_x3 with six unit kinds: 4.5 KB of scratch per lane, 231 VGPRs).
 __device__ __forceinline__ const float* seg_base(const FactorJobDev& J, const float* const* segs,
                                                  int seg) {
-  return J.seg_off >= 0 ? segs[J.seg_off + seg] : J.x.ptr;
+  const float* queued = segs[max(J.seg_off, 0) + seg];
+  const float* single = J.x.ptr;
+  return J.seg_off >= 0 ? queued : single;
 }
 
 // rows of batch `seg` of a job (its ragged last batch: x.last_rows).  Arithmetic, not a
@@ -312,24 +321,51 @@ int launch_syrk3(const FactorArgs& args, int tasks, hipStream_t stream);
 // graph whose edge (p, q) is the 32 x 32 block (p, q), and a unit is a clique of up to four
 // panels whose workgroup splits each panel's fragment once and multiplies every pair of
 // them -- a K4 is 6 blocks on 4 splits where a 64 x 64 tile is 4 blocks on 4.  The table of
-// a P is an exact partition of the lower triangle: every block p > q in exactly one K4, K3
-// or K2, every diagonal block in exactly one diagonal unit (up to four panels' (p, p)).
+// a P is an exact partition of the lower triangle: every block p > q in exactly one unit,
+// every diagonal block in exactly one -- K4, K3, K2, diagonal units (up to four panels'
+// (p, p)) and the two mixed kinds below.
 // P = 25 (the MNIST MLP's 785) is the Steiner system S(2, 4, 25): 50 K4 units, 200 fragment
 // splits for its 300 off-diagonal blocks; other P are packed greedily in a fixed order.
+// Two mixed kinds take the pairs the cliques leave single together with diagonal blocks
+// (panel slots ascending, as in a clique): S3D3, four slots, the blocks (3, 0), (3, 1),
+// (3, 2) of the hub slot 3 and the diagonal blocks of slots 0, 1, 2 -- a K4's six blocks
+// on its four splits; P1D2, two slots, (1, 0), (0, 0) and (1, 1).  P = 5 (the MLP's 129)
+// is a K4, an S3D3 and a P1D2.
 // One 32-bit entry per unit: panel s in bits 6s .. 6s+5 (unused slots repeat the last
-// panel), the number of panels in bits 24-26, bit 28 a diagonal unit.
+// panel), the number of panels in bits 24-26, bit 28 a diagonal unit, bits 29-30 a mixed
+// kind (X3_MIX_*; 0: a clique or a diagonal unit).
 constexpr int X3_WGS = 4;     // (of two waves -- 3 or 2 measured slower)
 constexpr int X3_PMAX = 64;   // panels per edge the 6-bit panel fields hold (n <= 2048)
 constexpr int X3_UCAP = 2048; // table entries one launch carries (8 KB of kernel arguments)
 constexpr uint32_t X3_DIAG = 1u << 28;
+constexpr int X3_MIX_S3D3 = 1, X3_MIX_P1D2 = 2;
 struct X3Units {
   uint32_t u[X3_UCAP];
 };
 __host__ __device__ inline int x3_unit_np(uint32_t u) { return (int)(u >> 24) & 7; }
 __host__ __device__ inline int x3_unit_panel(uint32_t u, int s) { return (int)(u >> (6 * s)) & 63; }
+__host__ __device__ inline int x3_unit_mix(uint32_t u) { return (int)(u >> 29) & 3; }
 static inline int x3_panels(int n) { return (n + 31) / 32; }
-// the unit table of P panels (2 <= P <= X3_PMAX; built once per P, then shared) -- K4
-// units first, then the diagonal units, K3 and K2: the longest first
+// The launch-wide split-major task order of kfac_factor_tiles_x3 (FactorArgs::split_major
+// == 2: every job at `splits` K-splits): with U the launch's units per split (a narrow job
+// is one unit), logical task t -- xcd_task of workgroup `block` of `blocks` = U splits --
+// is split t / U and launch-wide unit t % U, the jobs' units in job order: unit_end[j] =
+// the units of jobs 0 .. j (FactorArgs::task_end in this order; task_begin likewise).
+// xcd_task hands every XCD a contiguous range of t: where 8 divides the splits, whole
+// splits -- each operand row is then fetched into one L2 only, and every XCD gets the
+// same mix of units.
+__host__ __device__ __forceinline__ void x3_task_decode(const int* unit_end, int njobs, int splits,
+                                                        int blocks, int block, int& job, int& unit, int& split) {
+  const int U = blocks / splits;
+  const int t = xcd_task(block, blocks);
+  split = t / U;
+  const int lu = t - split * U;
+  job = 0;
+  while (job + 1 < njobs && lu >= unit_end[job]) ++job;
+  unit = lu - (job > 0 ? unit_end[job - 1] : 0);
+}
+// the unit table of P panels (2 <= P <= X3_PMAX; built once per P, then shared) -- K4 and
+// S3D3 units first, then the diagonal units, K3, P1D2 and K2: the longest first
 int x3_unit_table(int P, const uint32_t** table);
 // units of a factor of n (n <= 32: the one narrow task)
 int x3_units(int n);

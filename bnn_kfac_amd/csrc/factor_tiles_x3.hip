@@ -84,15 +84,34 @@ __device__ __forceinline__ void x3_pattern() {  // 6 MFMAs, NV VALU each, the re
 // panel), or the diagonal blocks (s, s) of four panel slots.  Accumulators, in order:
 //   K4: (1,0) (2,0) (2,1) (3,0) (3,1) (3,2);  K3 and K2: the first 3 / 1 of them;
 //   X3_KDIAG: (0,0) (1,1) (2,2) (3,3).
-constexpr int X3_KDIAG = 0;
+// The mixed kinds (factor_common.h) -- a diagonal block is x3_six(acc, F, F), as in the
+// diagonal kind:
+//   X3_KS3D3: (3,0) (3,1) (3,2) (0,0) (1,1) (2,2);  X3_KP1D2: (1,0) (0,0) (1,1).
+constexpr int X3_KDIAG = 0, X3_KS3D3 = 5, X3_KP1D2 = 6;
 constexpr int X3_NACC = 6;  // (a K4's: the LDS hand-off's slots)
-__host__ __device__ constexpr int x3_kind_blocks(int kind) { return kind == X3_KDIAG ? 4 : kind * (kind - 1) / 2; }
+__host__ __device__ constexpr int x3_kind_slots(int kind) {
+  return kind == X3_KDIAG || kind == X3_KS3D3 ? 4 : kind == X3_KP1D2 ? 2 : kind;
+}
+__host__ __device__ constexpr int x3_kind_blocks(int kind) {
+  return kind == X3_KDIAG ? 4 : kind == X3_KS3D3 ? 6 : kind == X3_KP1D2 ? 3 : kind * (kind - 1) / 2;
+}
+// (slot of block b's row / column panel, by the accumulator orders above)
+struct X3Block {
+  int i, j;
+};
+__host__ __device__ constexpr X3Block x3_kind_block(int kind, int b) {
+  constexpr int BI[6] = {1, 2, 2, 3, 3, 3}, BJ[6] = {0, 0, 1, 0, 1, 2};
+  if (kind == X3_KDIAG) return {b & 3, b & 3};
+  if (kind == X3_KS3D3) return b < 3 ? X3Block{3, b} : X3Block{b - 3, b - 3};
+  if (kind == X3_KP1D2) return b == 0 ? X3Block{1, 0} : X3Block{b - 1, b - 1};
+  return {BI[b], BJ[b]};
+}
 
 template <int KIND, bool FILL>
 __device__ __forceinline__ void x3_loop(const FactorJobDev& J, const float* const* segs, const int (&pn)[4],
                                         int64_t s0, int64_t s1, floatx16 (&acc)[x3_kind_blocks(KIND)]) {
   constexpr bool DIAG = KIND == X3_KDIAG;
-  constexpr int NP = DIAG ? 4 : KIND;
+  constexpr int NP = x3_kind_slots(KIND);
   static_assert(NP >= 2 && NP <= 4, "a unit has two to four panel slots");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -196,6 +215,43 @@ __device__ __forceinline__ void x3_loop(const FactorJobDev& J, const float* cons
       F1n = take(1, kn, kns, c2);
       x3_six(acc[3], F3, F3);
       x3_pattern<NV>();
+    } else if constexpr (KIND == X3_KS3D3) {
+      // (0,0) | split F3    (3,0) | split F2    (1,1) | split F0'
+      // (3,1)               (2,2) | split F1'   (3,2)
+      // (a K4's six segments and four splits; F0 and F1 end before F0' and F1' are split)
+      const X3Frag F3 = take(3, kc, kcs, c1);
+      x3_six(acc[3], F0, F0);
+      x3_pattern<NV>();
+      __builtin_amdgcn_sched_barrier(0);
+      const X3Frag F2 = take(2, kc, kcs, c1);
+      x3_six(acc[0], F3, F0);
+      x3_pattern<NV>();
+      __builtin_amdgcn_sched_barrier(0);
+      F0n = take(0, kn, kns, c2);
+      x3_six(acc[4], F1, F1);
+      x3_pattern<NV>();
+      __builtin_amdgcn_sched_barrier(0);
+      x3_six(acc[1], F3, F1);
+      x3_pattern<0>();
+      __builtin_amdgcn_sched_barrier(0);
+      F1n = take(1, kn, kns, c2);
+      x3_six(acc[5], F2, F2);
+      x3_pattern<NV>();
+      __builtin_amdgcn_sched_barrier(0);
+      x3_six(acc[2], F3, F2);
+      x3_pattern<0>();
+    } else if constexpr (KIND == X3_KP1D2) {
+      // (1,0) | split F0'   (0,0) | split F1'   (1,1)
+      F0n = take(0, kn, kns, c2);
+      x3_six(acc[0], F1, F0);
+      x3_pattern<NV>();
+      __builtin_amdgcn_sched_barrier(0);
+      F1n = take(1, kn, kns, c2);
+      x3_six(acc[1], F0, F0);
+      x3_pattern<NV>();
+      __builtin_amdgcn_sched_barrier(0);
+      x3_six(acc[2], F1, F1);
+      x3_pattern<0>();
     } else if constexpr (NP == 4) {
       const X3Frag F2 = take(2, kc, kcs, c1);
       x3_six(acc[0], F1, F0);
@@ -298,9 +354,8 @@ __device__ __forceinline__ void x3_unit(const FactorJobDev& J, const float* cons
   for (int b = 0; b < NB; ++b) {
     const bool mine = (b < HALF) == (wave == 0);
     if (b >= nblk || !mine) continue;
-    // (slot of the block's row / column panel, by the accumulator order above)
-    constexpr int BI[6] = {1, 2, 2, 3, 3, 3}, BJ[6] = {0, 0, 1, 0, 1, 2};
-    const int pr = DIAG ? pn[b & 3] : pn[BI[b]], pc = DIAG ? pn[b & 3] : pn[BJ[b]];
+    const X3Block blk = x3_kind_block(KIND, b);  // (b: unrolled, a constant)
+    const int pr = pn[blk.i], pc = pn[blk.j];
     const int ti = pr >> 1, tj = pc >> 1;
     float* out = J.slab + ((size_t)(ti * (ti + 1) / 2 + tj) * J.sstride + split) * TILE * TILE +
                  (pr & 1) * 32 * TILE + (pc & 1) * 32;
@@ -312,19 +367,18 @@ __device__ __forceinline__ void x3_unit(const FactorJobDev& J, const float* cons
 
 template <int GBK>
 __device__ __forceinline__ void factor_task_x3(const FactorJobDev& J, const float* const* segs,
-                                               const X3Units& U, int local, float* lds, int split_major) {
+                                               const X3Units& U, int unit, int split, float* lds) {
   static_assert(GBK == 16 * X3_NW, "one 16-row half stage per wave");
-  const int units = J.x3units;
-  const int split = split_major ? local / units : local % J.splits;
-  const int unit = split_major ? local - split * units : local / J.splits;
   const uint32_t u = U.u[J.x3tab + unit];
-  const int np = x3_unit_np(u);
+  const int np = x3_unit_np(u), mix = x3_unit_mix(u);
   const int pn[4] = {x3_unit_panel(u, 0), x3_unit_panel(u, 1), x3_unit_panel(u, 2), x3_unit_panel(u, 3)};
-  switch ((u & X3_DIAG) ? X3_KDIAG : np) {
+  switch (mix == X3_MIX_S3D3 ? X3_KS3D3 : mix == X3_MIX_P1D2 ? X3_KP1D2 : (u & X3_DIAG) ? X3_KDIAG : np) {
     case 4: x3_unit<4>(J, segs, pn, np, split, lds); break;
     case 3: x3_unit<3>(J, segs, pn, np, split, lds); break;
     case 2: x3_unit<2>(J, segs, pn, np, split, lds); break;
     case X3_KDIAG: x3_unit<X3_KDIAG>(J, segs, pn, np, split, lds); break;
+    case X3_KS3D3: x3_unit<X3_KS3D3>(J, segs, pn, np, split, lds); break;
+    case X3_KP1D2: x3_unit<X3_KP1D2>(J, segs, pn, np, split, lds); break;
     default: break;  // (not reached)
   }
 }
@@ -337,22 +391,31 @@ __global__ __launch_bounds__(X3_THREADS, 2) void kfac_factor_tiles_x3(FactorArgs
   __shared__ __attribute__((aligned(16))) float lds[X3_NACC * 16 * 64];
   // (no start stagger here: the fp32 kernel's +2.5 % measured neutral on this one, MLP
   // line 1.951-1.954e8 without vs 1.951-1.957e8 with, 3 alternating runs, profiles/r06b/)
-  const int task = xcd_task(blockIdx.x, gridDim.x);
-  int j = 0;
-  while (j + 1 < args.njobs && task >= args.task_end[j]) ++j;
-  const int local = task - args.job[j].task_begin;
+  int j = 0, unit, split;
+  if (args.split_major == 2) {
+    // every job at the same K-splits: split-major across the launch (factor_common.h;
+    // task_end counts units here)
+    x3_task_decode(args.task_end, args.njobs, args.job[0].splits, gridDim.x, blockIdx.x, j, unit, split);
+  } else {
+    const int task = xcd_task(blockIdx.x, gridDim.x);
+    while (j + 1 < args.njobs && task >= args.task_end[j]) ++j;
+    const int local = task - args.job[j].task_begin;
+    const int nu = args.job[j].x3units, ns = args.job[j].splits;
+    split = args.split_major ? local / nu : local % ns;
+    unit = args.split_major ? local - split * nu : local / ns;
+  }
   const FactorJobDev& J = args.job[j];
   if (J.n <= 32)
-    factor_task_narrow_direct<X3_NW>(J, args.segs, local, lds);
+    factor_task_narrow_direct<X3_NW>(J, args.segs, split, lds);
   else
-    factor_task_x3<BK>(J, args.segs, units, local, lds, args.split_major);
+    factor_task_x3<BK>(J, args.segs, units, unit, split, lds);
 }
 
 // ------------------------------------------------------------------- host side
 namespace {
 
-uint32_t x3_pack(const int* p, int np, bool diag) {
-  uint32_t u = (uint32_t)np << 24 | (diag ? X3_DIAG : 0u);
+uint32_t x3_pack(const int* p, int np, bool diag, int mix = 0) {
+  uint32_t u = (uint32_t)np << 24 | (diag ? X3_DIAG : 0u) | (uint32_t)mix << 29;
   for (int s = 0; s < 4; ++s) u |= (uint32_t)p[std::min(s, np - 1)] << (6 * s);
   return u;
 }
@@ -362,11 +425,18 @@ uint32_t x3_pack(const int* p, int np, bool diag) {
 // it; their 24 differences are the 24 non-zero vectors, each once, so every panel pair
 // lies in exactly one of the 50 blocks (a Steiner system S(2, 4, 25)).  Any other P: the
 // first K4 in lexicographic order whose six pairs are all free, until none is left, then
-// K3s and K2s the same way; a pair is never taken twice, and the K2 pass takes every pair
-// still free, so the partition is exact whatever the packing's quality.
+// K3s the same way.  The pairs still free then -- one unit each as K2s -- are taken with
+// diagonal blocks where that saves units: three of them under one higher panel h, to
+// panels a < b < c whose diagonal blocks are free, are one S3D3 (a, b, c, h); a pair whose
+// two diagonal blocks are free is a P1D2; the rest are K2s, and the diagonal blocks still
+// free go four to a diagonal unit.  A pair or a diagonal block is never taken twice, and
+// the K2 and diagonal passes take every one still free, so the partition is exact
+// whatever the packing's quality.  (The K3s come before the mixed units: an S3D3 then
+// replaces three K2s and three quarters of a diagonal unit, a P1D2 one K2 and half of
+// one, so no P has more units than with cliques and diagonal units alone.)
 std::vector<uint32_t> x3_build_table(int P) {
-  std::vector<uint32_t> k4, k3, k2, dg;
-  std::vector<char> used((size_t)P * P, 0);
+  std::vector<uint32_t> k4, s3, k3, p1, k2, dg;
+  std::vector<char> used((size_t)P * P, 0), dused(P, 0);
   auto is_free = [&](int a, int b) { return !used[(size_t)a * P + b]; };
   auto mark = [&](int a, int b) { used[(size_t)a * P + b] = used[(size_t)b * P + a] = 1; };
   if (P == 25) {
@@ -405,21 +475,45 @@ std::vector<uint32_t> x3_build_table(int P) {
           mark(a, b), mark(a, c), mark(b, c);
           k3.push_back(x3_pack(p, 3, false));
         }
+  for (int h = 0; h < P; ++h) {  // the stars of the hub h
+    int p[4], np = 0;
+    for (int a = 0; a < h; ++a) {
+      if (!is_free(a, h) || dused[a]) continue;
+      p[np++] = a;
+      if (np < 3) continue;
+      p[3] = h;
+      for (int i = 0; i < 3; ++i) mark(p[i], h), dused[p[i]] = 1;
+      s3.push_back(x3_pack(p, 4, false, X3_MIX_S3D3));
+      np = 0;
+    }
+  }
   for (int a = 0; a < P; ++a)
-    for (int b = a + 1; b < P; ++b)
-      if (is_free(a, b)) {
-        const int p[2] = {a, b};
-        mark(a, b);
+    for (int b = a + 1; b < P; ++b) {
+      if (!is_free(a, b)) continue;
+      const int p[2] = {a, b};
+      mark(a, b);
+      if (!dused[a] && !dused[b]) {
+        dused[a] = dused[b] = 1;
+        p1.push_back(x3_pack(p, 2, false, X3_MIX_P1D2));
+      } else {
         k2.push_back(x3_pack(p, 2, false));
       }
-  for (int a = 0; a < P; a += 4) {
+    }
+  {
     int p[4], np = 0;
-    for (; np < 4 && a + np < P; ++np) p[np] = a + np;
-    dg.push_back(x3_pack(p, np, true));
+    for (int a = 0; a < P; ++a) {
+      if (!dused[a]) p[np++] = a;
+      if (np == 4 || (np > 0 && a == P - 1)) {
+        dg.push_back(x3_pack(p, np, true));
+        np = 0;
+      }
+    }
   }
   std::vector<uint32_t> t(k4);
+  t.insert(t.end(), s3.begin(), s3.end());
   t.insert(t.end(), dg.begin(), dg.end());
   t.insert(t.end(), k3.begin(), k3.end());
+  t.insert(t.end(), p1.begin(), p1.end());
   t.insert(t.end(), k2.begin(), k2.end());
   return t;
 }
@@ -487,9 +581,33 @@ extern "C" int kfac_x3_unit_table(int P, int32_t* out, int cap) {
   for (int i = 0; i < nu && i < cap && out; ++i) {
     const int np = kfac::x3_unit_np(t[i]);
     const bool diag = (t[i] & kfac::X3_DIAG) != 0;
+    const int mix = kfac::x3_unit_mix(t[i]);
     for (int s = 0; s < 4; ++s) out[6 * i + s] = s < np ? kfac::x3_unit_panel(t[i], s) : -1;
-    out[6 * i + 4] = diag ? 0 : (np == 4 ? 63 : np == 3 ? 0b001011 : 0b000001);
-    out[6 * i + 5] = diag ? (1 << np) - 1 : 0;
+    out[6 * i + 4] = mix == kfac::X3_MIX_S3D3 ? 0b110100 : mix == kfac::X3_MIX_P1D2 ? 0b000001
+                     : diag ? 0 : (np == 4 ? 63 : np == 3 ? 0b001011 : 0b000001);
+    out[6 * i + 5] = mix == kfac::X3_MIX_S3D3 ? 0b0111 : mix == kfac::X3_MIX_P1D2 ? 0b0011
+                     : diag ? (1 << np) - 1 : 0;
   }
   return nu;
+}
+
+// Workgroup `block`'s task in the launch-wide split-major order (include/kfac_hip.h)
+extern "C" int kfac_x3_task_decode(const int32_t* units, int njobs, int splits, int blocks, int block,
+                                   int32_t* xcd_job_unit_split) {
+  if (!units || !xcd_job_unit_split || njobs < 1 || njobs > kfac::MAXJ || splits < 1) return KFAC_EINVAL;
+  int64_t U = 0;
+  int unit_end[kfac::MAXJ];
+  for (int i = 0; i < njobs; ++i) {
+    if (units[i] < 1 || units[i] > kfac::X3_UCAP) return KFAC_EINVAL;
+    U += units[i];
+    unit_end[i] = (int)U;
+  }
+  if (U * splits != blocks || block < 0 || block >= blocks) return KFAC_EINVAL;
+  int job, unit, split;
+  kfac::x3_task_decode(unit_end, njobs, splits, blocks, block, job, unit, split);
+  xcd_job_unit_split[0] = block & 7;
+  xcd_job_unit_split[1] = job;
+  xcd_job_unit_split[2] = unit;
+  xcd_job_unit_split[3] = split;
+  return KFAC_OK;
 }

@@ -146,6 +146,16 @@ KFAC_API int kfac_factor_flush(const kfac_factor_job* jobs, int njobs, kfac_stre
  * panels whose diagonal block it owns.  Fills at most cap units; returns the number of
  * units of the table (0: P out of range).                                           */
 KFAC_API int kfac_x3_unit_table(int P, int32_t* out, int cap);
+/* The task workgroup `block` of a kfac_factor_tiles_x3 launch computes when every one of
+ * its njobs jobs has `splits` K-splits, for inspection; no GPU needed.  units[j] = units of
+ * job j (kfac_x3_unit_table's count; 1 for a factor of n <= 32); `blocks` = splits x the sum
+ * of units[], the launch's workgroups.  xcd_job_unit_split[0..3] = the XCD the workgroup is
+ * dispatched to (block % 8), the job, the job's unit and the K-split, exactly as the kernel
+ * decodes them: split-major across the launch, every XCD a contiguous range of that order.
+ * KFAC_EINVAL: null pointers, njobs outside 1..16, a count below 1, blocks not splits x
+ * the units, block outside 0..blocks-1.                                              */
+KFAC_API int kfac_x3_task_decode(const int32_t* units, int njobs, int splits, int blocks, int block,
+                        int32_t* xcd_job_unit_split);
 
 /* Single-factor conveniences (same kernels). */
 KFAC_API int kfac_syrk_linear(const float* x, int64_t B, int64_t d, int64_t ldx, int has_ones,
