@@ -291,6 +291,10 @@ for _name, _job in (("kfac_kron_cov_full_tiled", CovFullJob), ("kfac_kron_cov_ou
                                                                 ctypes.c_int, ctypes.c_int])
     SIGNATURES[_name] = (ctypes.c_int, [ctypes.POINTER(_job), ctypes.c_int, c_i64, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp])
+# the class-tiled INF covariance calls: the capped calls' job structs and arguments
+for _name in ("kfac_inf_cov", "kfac_inf_cov_outer"):
+    SIGNATURES[_name + "_tiled_workspace_bytes"] = SIGNATURES[_name + "_workspace_bytes"]
+    SIGNATURES[_name + "_tiled"] = SIGNATURES[_name]
 
 _lib = None
 _lock = threading.Lock()
@@ -886,6 +890,36 @@ def inf_cov_outer(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = 
     ws = workspace.get(out.device, need)
     check(L.kfac_inf_cov_outer(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
                                stream_handle(out.device)), "kfac_inf_cov_outer")
+
+
+def inf_cov_tiled_workspace_bytes(jobs, nb: int, nc: int) -> int:
+    return lib().kfac_inf_cov_tiled_workspace_bytes(as_array(InfCovJob, jobs), len(jobs), nb, nc)
+
+
+def inf_cov_tiled(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_inf_cov_tiled: inf_cov for any nc (64x64 class tiles), <= 8 jobs."""
+    _blocks_out(out, nb, nc, "inf_cov_tiled")
+    L = lib()
+    arr = as_array(InfCovJob, jobs)
+    need = L.kfac_inf_cov_tiled_workspace_bytes(arr, len(jobs), nb, nc)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_inf_cov_tiled(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
+                               stream_handle(out.device)), "kfac_inf_cov_tiled")
+
+
+def inf_cov_outer_tiled_workspace_bytes(jobs, nb: int, nc: int) -> int:
+    return lib().kfac_inf_cov_outer_tiled_workspace_bytes(as_array(InfCovOuterJob, jobs), len(jobs), nb, nc)
+
+
+def inf_cov_outer_tiled(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_inf_cov_outer_tiled: inf_cov_outer for any nc (64x64 class tiles), <= 8 jobs."""
+    _blocks_out(out, nb, nc, "inf_cov_outer_tiled")
+    L = lib()
+    arr = as_array(InfCovOuterJob, jobs)
+    need = L.kfac_inf_cov_outer_tiled_workspace_bytes(arr, len(jobs), nb, nc)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_inf_cov_outer_tiled(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
+                                     stream_handle(out.device)), "kfac_inf_cov_outer_tiled")
 
 
 def sample(jobs, device: torch.device, accumulate: bool) -> None:

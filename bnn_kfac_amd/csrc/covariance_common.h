@@ -7,7 +7,8 @@
 // Abar^T panel, and the 64x64 Gram tile all three of their operands go through; the
 // class-tiled per-sample calls (covariance_tiled.hip) run that tile on one sample's rows; the
 // class-tiled weighted calls (covariance_wtiled.hip) take the sweep / per-entry calls' job
-// checks and projection launches and the tiled calls' row and tile-pair counts; the draw calls (covariance_draws.hip) start from the same apply / U / V launches.
+// checks and projection launches and the tiled calls' row and tile-pair counts, and share their
+// weighted panel with the class-tiled INF calls (covariance_inf_tiled.hip); the draw calls (covariance_draws.hip) start from the same apply / U / V launches.
 #pragma once
 
 #include "kfac_common.h"
@@ -457,5 +458,66 @@ __device__ __forceinline__ void cov_joint_gram_tile(const float* X, int64_t K, i
 #pragma unroll
   for (int v = 0; v < 16; ++v) dst[acc_row(v, lane) * TILE] = acc[v];
 }
+
+// ---- the weighted tile operand of the class-tiled weighted calls (covariance_wtiled.hip) and
+// of the class-tiled INF calls' first term (covariance_inf_tiled.hip)
+constexpr int KFAC_WCHANNEL = 23;  // (k, j) = w[k] * X[j*ld + k]
+
+// X (rows x K, K contiguous per row, rows ld >= K apart) with row k of the panel scaled by w[k]
+__device__ __forceinline__ OpDev wchannel_op(const float* X, int64_t K, int64_t ld, int rows, const float* wA,
+                                             const float* wG, int nG, int mode) {
+  OpDev d{};
+  d.ptr = X; d.layout = KFAC_WCHANNEL; d.rows = K; d.cols = rows; d.L = ld; d.ones = -1;
+  d.sB = aux_bits(wG); d.ld = aux_bits(wA); d.C = nG; d.H = mode;
+  return d;
+}
+
+// Panel<CHANNEL>'s thread map (32 lanes walk k, contiguous in a row of X); a thread's k row
+// has ONE weight per stage, read (rank one: formed) once and applied to its 8 elements.
+// Loads are issued for k_first, k_first + BK, ... in order, so (a, g) of the thread's row is
+// advanced, not divided.
+template <>
+struct Panel<KFAC_WCHANNEL> {
+  static constexpr int PITCH = LDP;
+  const float* base;
+  const float* wA;
+  const float* wG;
+  int64_t L, kend, kk, ia;  // kk: row k + r of the next load, (ia, ig) its (a, g)
+  int r, c0, col0, cols, nG, ig;
+  bool rank1;
+  __device__ __forceinline__ void init(const OpDev& op, const float* base_, int col0_, int tid,
+                                       int64_t k_end, int64_t k_first) {
+    base = base_; wG = aux_ptr(op.sB); wA = aux_ptr(op.ld); L = op.L; kend = k_end; cols = op.cols;
+    nG = op.C; rank1 = op.H == WGRAM_RANK1;
+    r = tid & 31; c0 = tid >> 5; col0 = col0_;
+    kk = k_first + r;
+    ia = 0; ig = 0;
+    if (rank1) {
+      ia = kk / nG;
+      ig = (int)(kk - ia * nG);
+    }
+  }
+  __device__ __forceinline__ void load(int64_t, float (&v)[8]) {
+    const bool ok = kk < kend;
+    float w = 0.f;
+    if (ok) w = rank1 ? wA[ia] * wG[ig] : wG[kk];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const int col = col0 + c0 + 8 * m;
+      float x = 0.f;
+      if (ok && col < cols) x = w * base[(int64_t)col * L + kk];
+      v[m] = x;
+    }
+    kk += BK;
+    if (rank1) {
+      ig += BK;
+      while (ig >= nG) { ig -= nG; ++ia; }
+    }
+  }
+  __device__ __forceinline__ void store(float* lds, const float (&v)[8]) const {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) lds[r * LDP + c0 + 8 * m] = v[m];
+  }
+};
 
 }  // namespace kfac

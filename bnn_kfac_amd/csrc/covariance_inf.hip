@@ -28,7 +28,7 @@
 //   reduce: kfac_inf_reduce.
 // No atomics, plain vector stores; the diagonal is a difference of two non-negative sums and
 // is not clamped (kfac_hip.h).
-#include "covariance_common.h"
+#include "covariance_inf.h"
 
 namespace kfac {
 
@@ -186,37 +186,6 @@ struct Panel<KFAC_INF_WJ> {
           make_float4(v[4 * m], v[4 * m + 1], v[4 * m + 2], v[4 * m + 3]);
   }
 };
-
-struct InfJobDev {
-  const float* a;   // outer route
-  const float* D;
-  const float* J;   // dense route
-  const float* UA;
-  const float* UG;
-  const float* W;
-  const float* F;
-  float* HX;        // outer: HR, nb x (ra+1) x nG; dense: X, rows x ra x nG
-  float* T;         // rows x r
-  float* Y;         // rows x r
-  float* part1;     // nb x nseg1 x nc*nc
-  float* part2;     // nb x nseg2 x nc*nc
-  int64_t lda, ldD, ldJ, ldA, ldG, ldF;
-  int cols, ones, nA, nG, ra, rg, r;
-  int hcols;        // columns of the h / x launch's wide operand: nb*(ra+1) / rows*nG
-  int trows;        // rows*ra
-  int hn, tn, yn;   // tiles along the second tile index of the h|x / t / y launch
-  int nseg1, nseg2;
-  int h_begin, t_begin, y_begin, g1_begin, g2_begin;
-};
-
-struct InfArgs {
-  int njobs, nc, accumulate, rows;  // rows = nb*nc
-  int64_t nb;
-  float* cov;
-  int h_end[CMAXJ], t_end[CMAXJ], y_end[CMAXJ], g1_end[CMAXJ], g2_end[CMAXJ];
-  InfJobDev job[CMAXJ];
-};
-static_assert(sizeof(InfArgs) <= 4096, "kernel argument block");
 
 __device__ __forceinline__ void zero(floatx16& acc) {
 #pragma unroll
@@ -390,23 +359,6 @@ static bool inf_call_ok(const void* jobs, int njobs, int64_t nb, int nc) {
   return jobs && njobs > 0 && njobs <= CMAXJ && nb > 0 && nc > 0 && nc <= CMAXC;
 }
 
-// What both routes share once a job is reduced to (nA, nG, ra, rg): sizes of T / Y and the
-// Gram partials.  hx: floats of the route's first intermediate.
-struct InfDims {
-  int64_t nA, nG, ra, rg, k1;  // k1: the first term's Gram length (nG, or nA*nG)
-  size_t hx;
-};
-static InfDims inf_dims(const kfac_inf_cov_job& q, int64_t nb, int nc) {
-  return InfDims{q.nA, q.nG, q.ra, q.rg, (int64_t)q.nA * q.nG, (size_t)(nb * nc) * (size_t)q.ra * (size_t)q.nG};
-}
-static InfDims inf_dims(const kfac_inf_cov_outer_job& q, int64_t nb, int) {
-  return InfDims{(int64_t)q.cols + (q.has_ones != 0), q.nG, q.ra, q.rg, q.nG,
-                 (size_t)nb * (size_t)(q.ra + 1) * (size_t)q.nG};
-}
-static size_t inf_hx_bytes(const InfDims& d) { return align_up(d.hx * sizeof(float), 256); }
-static size_t inf_ty_bytes(const InfDims& d, int64_t rows) {
-  return align_up((size_t)rows * (size_t)(d.ra * d.rg) * sizeof(float), 256);
-}
 static size_t inf_part_bytes(int64_t K, int64_t seg, int64_t nb, int nc) {
   return align_up((size_t)(nb * cdiv(K, seg)) * nc * nc * sizeof(float), 256);
 }
@@ -415,60 +367,49 @@ static size_t inf_job_bytes(const InfDims& d, int64_t nb, int nc) {
          inf_part_bytes(d.ra * d.rg, ISEG, nb, nc);
 }
 
-static bool inf_job_ok(const kfac_inf_cov_job& q) {
-  return q.J && q.UA && q.UG && q.W && q.F && q.nA > 0 && q.nG > 0 && q.ra > 0 && q.rg > 0 &&
-         q.ldJ >= (int64_t)q.nA * q.nG && q.ldA >= q.ra && q.ldG >= q.rg && q.ldW >= (int64_t)q.nA * q.nG &&
-         q.ldF >= (int64_t)q.ra * q.rg;
-}
-static bool inf_outer_job_ok(const kfac_inf_cov_outer_job& q) {
-  return q.a && q.D && q.UA && q.UG && q.W && q.F && q.cols > 0 && q.nG > 0 && q.ra > 0 && q.rg > 0 &&
-         q.lda >= q.cols && q.ldD >= q.nG && q.ldA >= q.ra && q.ldG >= q.rg &&
-         q.ldW >= ((int64_t)q.cols + (q.has_ones != 0)) * q.nG && q.ldF >= (int64_t)q.ra * q.rg;
-}
-
-// The shared part of job i's device block, its task ranges (m_tiles x n_tiles of the h | x
-// launch given by the caller) and its workspace slices.  false where a 32-bit column, row or
-// task count would overflow.
+// Job i's device block: the projection part (inf_fill_proj), then the task ranges of the two
+// Gram launches (n[3], n[4]) and their partials.  false where a 32-bit column, row or task
+// count would overflow.
 static bool inf_fill(InfArgs& args, int i, const InfDims& d, int64_t hcols, int64_t hm, int64_t hn, char*& ws,
                      int64_t (&n)[5]) {
   const int64_t lim = ((int64_t)1 << 31) - TILE;
-  const int64_t nb = args.nb, rows = args.rows, r = d.ra * d.rg;
+  const int64_t nb = args.nb, r = d.ra * d.rg;
   const int nc = args.nc;
-  if (d.nA >= lim || r >= lim || hcols >= lim || rows * d.ra >= lim || d.k1 >= lim * WSEG) return false;
+  if (d.k1 >= lim * WSEG) return false;
+  if (!inf_fill_proj(args, i, d, hcols, hm, hn, ws, n)) return false;
   InfJobDev& C = args.job[i];
-  C.nA = (int)d.nA; C.nG = (int)d.nG; C.ra = (int)d.ra; C.rg = (int)d.rg; C.r = (int)r;
-  C.hcols = (int)hcols;
-  C.trows = (int)(rows * d.ra);
-  C.hn = (int)hn;
-  C.tn = (int)cdiv(d.rg, TILE);
-  C.yn = (int)cdiv(r, TILE);
   C.nseg1 = (int)cdiv(d.k1, WSEG);
   C.nseg2 = (int)cdiv(r, ISEG);
-  C.h_begin = (int)n[0]; C.t_begin = (int)n[1]; C.y_begin = (int)n[2];
   C.g1_begin = (int)n[3]; C.g2_begin = (int)n[4];
-  n[0] += hm * hn;
-  n[1] += cdiv(C.trows, TILE) * C.tn;
-  n[2] += cdiv(rows, TILE) * C.yn;
   n[3] += nb * C.nseg1;
   n[4] += nb * C.nseg2;
-  for (int k = 0; k < 5; ++k)
-    if (n[k] >= lim) return false;
-  args.h_end[i] = (int)n[0]; args.t_end[i] = (int)n[1]; args.y_end[i] = (int)n[2];
+  if (n[3] >= lim || n[4] >= lim) return false;
   args.g1_end[i] = (int)n[3]; args.g2_end[i] = (int)n[4];
   if (ws) {
-    C.HX = reinterpret_cast<float*>(ws); ws += inf_hx_bytes(d);
-    C.T = reinterpret_cast<float*>(ws); ws += inf_ty_bytes(d, rows);
-    C.Y = reinterpret_cast<float*>(ws); ws += inf_ty_bytes(d, rows);
     C.part1 = reinterpret_cast<float*>(ws); ws += inf_part_bytes(d.k1, WSEG, nb, nc);
     C.part2 = reinterpret_cast<float*>(ws); ws += inf_part_bytes(r, ISEG, nb, nc);
   }
   return true;
 }
 
-// y, the second term's Gram partials and the reduce: the same for both routes.
-static int inf_launch_tail(const InfArgs& args, const int64_t (&n)[5], hipStream_t s) {
+int inf_launch_proj(const InfArgs& args, bool outer, const int64_t* n, hipStream_t s) {
+  if (outer)
+    hipLaunchKernelGGL(kfac_inf_h, dim3((unsigned)n[0]), dim3(NTHREADS), 0, s, args);
+  else
+    hipLaunchKernelGGL(kfac_inf_x, dim3((unsigned)n[0]), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
+  if (outer)
+    hipLaunchKernelGGL(kfac_inf_t<true>, dim3((unsigned)n[1]), dim3(NTHREADS), 0, s, args);
+  else
+    hipLaunchKernelGGL(kfac_inf_t<false>, dim3((unsigned)n[1]), dim3(NTHREADS), 0, s, args);
+  KFAC_CHECK_LAUNCH();
   hipLaunchKernelGGL(kfac_inf_y, dim3((unsigned)n[2]), dim3(NTHREADS), 0, s, args);
   KFAC_CHECK_LAUNCH();
+  return KFAC_OK;
+}
+
+// The second term's Gram partials and the reduce: the same for both routes.
+static int inf_launch_tail(const InfArgs& args, const int64_t (&n)[5], hipStream_t s) {
   hipLaunchKernelGGL(kfac_inf_gram2, dim3((unsigned)n[4]), dim3(NTHREADS), 0, s, args);
   KFAC_CHECK_LAUNCH();
   hipLaunchKernelGGL(kfac_inf_reduce, dim3((unsigned)args.nb), dim3(NTHREADS), 0, s, args);
@@ -509,19 +450,15 @@ extern "C" int kfac_inf_cov(const kfac_inf_cov_job* jobs, int njobs, int64_t nb,
   int64_t n[5] = {0, 0, 0, 0, 0};
   for (int i = 0; i < njobs; ++i) {
     const kfac_inf_cov_job& q = jobs[i];
-    InfJobDev& C = args.job[i];
-    C.J = q.J; C.UA = q.UA; C.UG = q.UG; C.W = q.W; C.F = q.F;
-    C.ldJ = q.ldJ; C.ldA = q.ldA; C.ldG = q.ldG; C.ldF = q.ldF;
-    const int64_t hcols = (int64_t)args.rows * q.nG;
-    if (!inf_fill(args, i, inf_dims(q, nb, nc), hcols, cdiv(q.ra, TILE), cdiv(hcols, TILE), ws, n))
-      return KFAC_EINVAL;
+    inf_set_operands(args.job[i], q);
+    int64_t hcols, hm, hn;
+    inf_h_shape(q, nb, nc, hcols, hm, hn);
+    if (!inf_fill(args, i, inf_dims(q, nb, nc), hcols, hm, hn, ws, n)) return KFAC_EINVAL;
   }
   if (!have) return KFAC_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(kfac_inf_x, dim3((unsigned)n[0]), dim3(NTHREADS), 0, s, args);
-  KFAC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(kfac_inf_t<false>, dim3((unsigned)n[1]), dim3(NTHREADS), 0, s, args);
-  KFAC_CHECK_LAUNCH();
+  const int rc = inf_launch_proj(args, false, n, s);
+  if (rc != KFAC_OK) return rc;
   hipLaunchKernelGGL(kfac_inf_gram1_dense, dim3((unsigned)n[3]), dim3(NTHREADS), 0, s, args);
   KFAC_CHECK_LAUNCH();
   return inf_launch_tail(args, n, s);
@@ -559,20 +496,15 @@ extern "C" int kfac_inf_cov_outer(const kfac_inf_cov_outer_job* jobs, int njobs,
   int64_t n[5] = {0, 0, 0, 0, 0};
   for (int i = 0; i < njobs; ++i) {
     const kfac_inf_cov_outer_job& q = jobs[i];
-    InfJobDev& C = args.job[i];
-    C.a = q.a; C.D = q.D; C.UA = q.UA; C.UG = q.UG; C.W = q.W; C.F = q.F;
-    C.lda = q.lda; C.ldD = q.ldD; C.ldA = q.ldA; C.ldG = q.ldG; C.ldF = q.ldF;
-    C.cols = q.cols; C.ones = q.has_ones ? q.cols : -1;
-    const int64_t hcols = nb * ((int64_t)q.ra + 1);
-    if (!inf_fill(args, i, inf_dims(q, nb, nc), hcols, cdiv(hcols, TILE), cdiv(q.nG, TILE), ws, n))
-      return KFAC_EINVAL;
+    inf_set_operands(args.job[i], q);
+    int64_t hcols, hm, hn;
+    inf_h_shape(q, nb, nc, hcols, hm, hn);
+    if (!inf_fill(args, i, inf_dims(q, nb, nc), hcols, hm, hn, ws, n)) return KFAC_EINVAL;
   }
   if (!have) return KFAC_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(kfac_inf_h, dim3((unsigned)n[0]), dim3(NTHREADS), 0, s, args);
-  KFAC_CHECK_LAUNCH();
-  hipLaunchKernelGGL(kfac_inf_t<true>, dim3((unsigned)n[1]), dim3(NTHREADS), 0, s, args);
-  KFAC_CHECK_LAUNCH();
+  const int rc = inf_launch_proj(args, true, n, s);
+  if (rc != KFAC_OK) return rc;
   hipLaunchKernelGGL(kfac_inf_gram1_outer, dim3((unsigned)n[3]), dim3(NTHREADS), 0, s, args);
   KFAC_CHECK_LAUNCH();
   return inf_launch_tail(args, n, s);

@@ -6,7 +6,8 @@
 // tiles, ntile = ceil(nc / 64), exactly as covariance_tiled.hip cuts it, and every tile pair
 // ti >= tj is a WEIGHTED Gram tile of that sample's projected rows X_b (nc x K):
 //   part[r][r'] = sum_{k in segment} X_b[r][k] * (w[k] * X_b[r'][k]) .
-// The A operand is the plain CHANNEL panel of tile ti's rows, the B operand Panel<KFAC_WCHANNEL>:
+// The A operand is the plain CHANNEL panel of tile ti's rows, the B operand Panel<KFAC_WCHANNEL>
+// (covariance_common.h: the class-tiled INF calls run it on their raw rows):
 // tile tj's rows times the k-row's weight as they are loaded (no product is stored), the way
 // Panel<KFAC_INF_WJ> forms w.M.  A diagonal tile therefore stages two panels; it still skips
 // its upper quadrant.  The weights of a task are w_base + t*stride_t + b*stride_b:
@@ -33,8 +34,6 @@
 
 namespace kfac {
 
-constexpr int KFAC_WCHANNEL = 23;  // (k, j) = w[k] * X[j*K + k]
-
 struct WTiledJobDev {
   const float* X;     // nb*nc x K, K contiguous per row
   float* partial;     // [grid point][sample][tile pair][segment][64 x 64]
@@ -54,63 +53,6 @@ struct WTiledArgs {
 };
 static_assert(sizeof(WTiledArgs) <= 4096, "kernel argument block");
 
-// X (rows x K, K contiguous per row) with row k of the panel scaled by w[k]
-__device__ __forceinline__ OpDev wchannel_op(const float* X, int64_t K, int rows, const float* wA,
-                                             const float* wG, int nG, int mode) {
-  OpDev d{};
-  d.ptr = X; d.layout = KFAC_WCHANNEL; d.rows = K; d.cols = rows; d.L = K; d.ones = -1;
-  d.sB = aux_bits(wG); d.ld = aux_bits(wA); d.C = nG; d.H = mode;
-  return d;
-}
-
-// Panel<CHANNEL>'s thread map (32 lanes walk k, contiguous in a row of X); a thread's k row
-// has ONE weight per stage, read (rank one: formed) once and applied to its 8 elements.
-// Loads are issued for k_first, k_first + BK, ... in order, so (a, g) of the thread's row is
-// advanced, not divided.
-template <>
-struct Panel<KFAC_WCHANNEL> {
-  static constexpr int PITCH = LDP;
-  const float* base;
-  const float* wA;
-  const float* wG;
-  int64_t L, kend, kk, ia;  // kk: row k + r of the next load, (ia, ig) its (a, g)
-  int r, c0, col0, cols, nG, ig;
-  bool rank1;
-  __device__ __forceinline__ void init(const OpDev& op, const float* base_, int col0_, int tid,
-                                       int64_t k_end, int64_t k_first) {
-    base = base_; wG = aux_ptr(op.sB); wA = aux_ptr(op.ld); L = op.L; kend = k_end; cols = op.cols;
-    nG = op.C; rank1 = op.H == WGRAM_RANK1;
-    r = tid & 31; c0 = tid >> 5; col0 = col0_;
-    kk = k_first + r;
-    ia = 0; ig = 0;
-    if (rank1) {
-      ia = kk / nG;
-      ig = (int)(kk - ia * nG);
-    }
-  }
-  __device__ __forceinline__ void load(int64_t, float (&v)[8]) {
-    const bool ok = kk < kend;
-    float w = 0.f;
-    if (ok) w = rank1 ? wA[ia] * wG[ig] : wG[kk];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const int col = col0 + c0 + 8 * m;
-      float x = 0.f;
-      if (ok && col < cols) x = w * base[(int64_t)col * L + kk];
-      v[m] = x;
-    }
-    kk += BK;
-    if (rank1) {
-      ig += BK;
-      while (ig >= nG) { ig -= nG; ++ia; }
-    }
-  }
-  __device__ __forceinline__ void store(float* lds, const float (&v)[8]) const {
-#pragma unroll
-    for (int m = 0; m < 8; ++m) lds[r * LDP + c0 + 8 * m] = v[m];
-  }
-};
-
 // Gram partial: one tile pair of one sample of one job over one K segment at one grid point.
 __global__ __launch_bounds__(NTHREADS) void kfac_cov_wtiled_gram(WTiledArgs args) {
   __shared__ __attribute__((aligned(16))) float lds[4 * PANEL];
@@ -126,7 +68,7 @@ __global__ __launch_bounds__(NTHREADS) void kfac_cov_wtiled_gram(WTiledArgs args
   const int64_t k0 = (int64_t)seg * JSEG, k1 = min(G.K, k0 + JSEG);
   const float* X = G.X + b * args.nc * G.K;
   const OpDev xa = channel_op(X, G.K, args.nc, G.K);
-  const OpDev xw = wchannel_op(X, G.K, args.nc, G.wA + (int64_t)t * G.ldwA,
+  const OpDev xw = wchannel_op(X, G.K, G.K, args.nc, G.wA + (int64_t)t * G.ldwA,
                                G.wG + (int64_t)t * G.stride_t + b * G.stride_b, G.nG, G.mode);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool active = !(ti == tj && wave == 1);  // quadrant (0, 1) of a diagonal tile

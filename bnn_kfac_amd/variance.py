@@ -1372,6 +1372,33 @@ def _inf_operands(UA: Tensor, UG: Tensor, W: Tensor, F: Tensor):
                             W.data_ptr(), W.numel(), F.data_ptr(), ld(F))
 
 
+def _inf_dense(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
+    """kron_covariance_inf / kron_covariance_inf_tiled: the terms parsed and checked, then
+    `call` per sample chunk (max_classes None: no cap)."""
+    if not terms:
+        raise ValueError("no terms")
+    parsed = []
+    nb = nc = None
+    for J, UA, UG, W, F in terms:
+        nA, nG, _, _ = _inf_shapes(UA, UG, W, F)
+        J3, ld = _cov_rows(J, nA * nG)
+        if nb is None:
+            nb, nc = J3.shape[0], J3.shape[1]
+        elif (J3.shape[0], J3.shape[1]) != (nb, nc):
+            raise ValueError("all terms need the same (nb, nc)")
+        if max_classes is not None and nc > max_classes:
+            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
+        parsed.append((J3, ld, nA, nG, UA, UG, W, F))
+    keep, jobs = [], []
+    for J3, ld, nA, nG, UA, UG, W, F in parsed:
+        N.require_device(J3, "J")
+        held, tail = _inf_operands(UA, UG, W, F)
+        keep.extend([J3, *held])
+        jobs.append((J3.data_ptr(), ld, nA, nG, *tail))
+    return _run_per_sample(jobs, N.InfCovJob, _cov_job_at, workspace_bytes, call, nb, nc, keep[0].device,
+                           max_workspace_bytes)
+
+
 def kron_covariance_inf(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
                         max_workspace_bytes: int = 1 << 30) -> Tensor:
     """cov[b, c, c'] = sum_l [ sum_{i,g} W_l[i, g] M_l[b, c][i, g] M_l[b, c'][i, g]
@@ -1385,43 +1412,35 @@ def kron_covariance_inf(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Te
     on that sample only (chunking under `max_workspace_bytes` changes no bit), two calls give
     identical bits, more than 8 terms fold in groups of 8.  The diagonal is a difference of two
     non-negative sums and is not clamped: it may come out negative at rounding level.  Shapes
-    are checked (ValueError) before anything touches the device.
+    are checked (ValueError) before anything touches the device.  At most MAX_COV_CLASSES
+    outputs: kron_covariance_inf_tiled has no cap.
     """
-    if not terms:
-        raise ValueError("no terms")
-    parsed = []
-    nb = nc = None
-    for J, UA, UG, W, F in terms:
-        nA, nG, _, _ = _inf_shapes(UA, UG, W, F)
-        J3, ld = _cov_rows(J, nA * nG)
-        if nb is None:
-            nb, nc = J3.shape[0], J3.shape[1]
-        elif (J3.shape[0], J3.shape[1]) != (nb, nc):
-            raise ValueError("all terms need the same (nb, nc)")
-        if nc > MAX_COV_CLASSES:
-            raise ValueError(f"kron_covariance_inf handles at most {MAX_COV_CLASSES} outputs, got {nc}")
-        parsed.append((J3, ld, nA, nG, UA, UG, W, F))
-    keep, jobs = [], []
-    for J3, ld, nA, nG, UA, UG, W, F in parsed:
-        N.require_device(J3, "J")
-        held, tail = _inf_operands(UA, UG, W, F)
-        keep.extend([J3, *held])
-        jobs.append((J3.data_ptr(), ld, nA, nG, *tail))
-    return _run_per_sample(jobs, N.InfCovJob, _cov_job_at, N.inf_cov_workspace_bytes, N.inf_cov, nb, nc,
-                           keep[0].device, max_workspace_bytes)
+    return _inf_dense(terms, "kron_covariance_inf", MAX_COV_CLASSES, N.inf_cov_workspace_bytes, N.inf_cov,
+                      max_workspace_bytes)
 
 
-def kron_covariance_outer_inf(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]],
+def kron_covariance_inf_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
                               max_workspace_bytes: int = 1 << 30) -> Tensor:
-    """kron_covariance_inf for Linear layers without their Jacobian rows (M[b, c] =
-    [a[b] | 1] D[b, c]^T): cov[b] = sum_l [ D_l[b] diag(rho_l[b]) D_l[b]^T - Y_l[b] Y_l[b]^T ],
-    rho[b][g] = sum_i abar[b][i]^2 W[i, g], Y[b][c] = F t[b, c],
-    t[b, c][p, q] = sum_g H[b][p, g] D[b, c][g] UG[g, q], H[b][p, g] = sum_i UA[i, p] abar[b][i] W[i, g].
+    """kron_covariance_inf for any number of outputs (a CIFAR-100 or ImageNet head): the same
+    terms, the same shape checks before anything touches the device, the same (nb, nc, nc)
+    fp32 result, nc not capped (kfac_inf_cov_tiled: a sample's block in 64x64 class tiles, the
+    weighted Gram of the raw rows and the Gram of F t kept as separate fp32 partials whose
+    difference is formed in fp64).
 
-    terms: [(a_l, D_l, UA_l, UG_l, W_l, F_l)], a (nb, cols) and D (nb, nc, nG) as
-    layer_io_jacobians returns them, UA (nA, ra) with nA = cols + 1 (bias: the ones column is
-    implicit) or nA = cols, UG, W, F as in kron_covariance_inf, whose guarantees hold.
+    Every block is bitwise symmetric; two calls give identical bits; a sample's block depends
+    on that sample only, so chunking under `max_workspace_bytes` changes no bit; padded strides
+    of J, UA, UG and F change no bit; terms fold in groups of 8; the diagonal is not clamped.
+    With F = 0 the result has the bits of kron_covariance_full_tiled on the same J and W with
+    identity VA, VG.  Against kron_covariance_inf (nc <= 32, another segmentation) it agrees to
+    fp32 rounding only.
     """
+    return _inf_dense(terms, "kron_covariance_inf_tiled", None, N.inf_cov_tiled_workspace_bytes,
+                      N.inf_cov_tiled, max_workspace_bytes)
+
+
+def _inf_outer(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
+    """kron_covariance_outer_inf / kron_covariance_outer_inf_tiled: the terms parsed and
+    checked, then `call` per sample chunk (max_classes None: no cap)."""
     if not terms:
         raise ValueError("no terms")
     parsed = []
@@ -1442,8 +1461,8 @@ def kron_covariance_outer_inf(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tens
             raise ValueError("all terms need the same (nb, nc)")
         if a2.shape[0] != nb:
             raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
-        if nc > MAX_COV_CLASSES:
-            raise ValueError(f"kron_covariance_outer_inf handles at most {MAX_COV_CLASSES} outputs, got {nc}")
+        if max_classes is not None and nc > max_classes:
+            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
         parsed.append((a2, cols, D3, ldD, nA, nG, UA, UG, W, F))
     keep, jobs = [], []
     for a2, cols, D3, ldD, nA, nG, UA, UG, W, F in parsed:
@@ -1455,8 +1474,48 @@ def kron_covariance_outer_inf(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tens
         held, tail = _inf_operands(UA, UG, W, F)
         keep.extend([a2, D3, *held])
         jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0, *tail))
-    return _run_per_sample(jobs, N.InfCovOuterJob, _cov_outer_job_at, N.inf_cov_outer_workspace_bytes,
-                           N.inf_cov_outer, nb, nc, keep[0].device, max_workspace_bytes)
+    return _run_per_sample(jobs, N.InfCovOuterJob, _cov_outer_job_at, workspace_bytes, call, nb, nc,
+                           keep[0].device, max_workspace_bytes)
+
+
+def kron_covariance_outer_inf(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]],
+                              max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_inf for Linear layers without their Jacobian rows (M[b, c] =
+    [a[b] | 1] D[b, c]^T): cov[b] = sum_l [ D_l[b] diag(rho_l[b]) D_l[b]^T - Y_l[b] Y_l[b]^T ],
+    rho[b][g] = sum_i abar[b][i]^2 W[i, g], Y[b][c] = F t[b, c],
+    t[b, c][p, q] = sum_g H[b][p, g] D[b, c][g] UG[g, q], H[b][p, g] = sum_i UA[i, p] abar[b][i] W[i, g].
+
+    terms: [(a_l, D_l, UA_l, UG_l, W_l, F_l)], a (nb, cols) and D (nb, nc, nG) as
+    layer_io_jacobians returns them, UA (nA, ra) with nA = cols + 1 (bias: the ones column is
+    implicit) or nA = cols, UG, W, F as in kron_covariance_inf, whose guarantees hold.  At most
+    MAX_COV_CLASSES outputs: kron_covariance_outer_inf_tiled has no cap.
+    """
+    return _inf_outer(terms, "kron_covariance_outer_inf", MAX_COV_CLASSES, N.inf_cov_outer_workspace_bytes,
+                      N.inf_cov_outer, max_workspace_bytes)
+
+
+def kron_covariance_outer_inf_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]],
+                                    max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_covariance_outer_inf for any number of outputs: the same terms and shape checks, nc
+    not capped (kfac_inf_cov_outer_tiled: 64x64 class tiles of D_b diag(rho_b) D_b^T on the raw
+    D rows and of Y_b Y_b^T, separate fp32 partials whose difference is formed in fp64).
+
+    kron_covariance_inf_tiled's guarantees hold: bitwise symmetric blocks, identical bits from
+    two calls, a sample's block depends on that sample only (chunking changes no bit), padded
+    strides of a, D, UA, UG and F change no bit, the diagonal is not clamped.  Against
+    kron_covariance_outer_inf (nc <= 32) and against kron_covariance_inf_tiled on the
+    materialised rows it agrees to fp32 rounding only.
+    """
+    return _inf_outer(terms, "kron_covariance_outer_inf_tiled", None, N.inf_cov_outer_tiled_workspace_bytes,
+                      N.inf_cov_outer_tiled, max_workspace_bytes)
+
+
+def _inf_calls(nc: int):
+    """(dense call, factored call) of the INF covariance for nc outputs: the capped calls up to
+    MAX_COV_CLASSES, the class-tiled ones above."""
+    if nc > MAX_COV_CLASSES:
+        return kron_covariance_inf_tiled, kron_covariance_outer_inf_tiled
+    return kron_covariance_inf, kron_covariance_outer_inf
 
 
 def _inf_layer_factors(inf, add, multiply, layers):
@@ -1505,10 +1564,11 @@ def inf_log_det(inf, add=0., multiply=1.) -> Tensor:
 
 
 def _inf_chunk(model, layers, factors, x, jacobians):
-    """(logits, cov (n, nc, nc)) of one chunk; factors[layer] = (UA, UG, W, F)."""
+    """(logits, cov (n, nc, nc)) of one chunk; factors[layer] = (UA, UG, W, F).  More than
+    MAX_COV_CLASSES outputs go through the class-tiled calls (_inf_calls)."""
     if jacobians == "dense":
         f, Js = output_jacobians(model, layers, x)
-        return f, kron_covariance_inf([(J, *factors[layer]) for layer, J in zip(layers, Js)])
+        return f, _inf_calls(f.shape[1])[0]([(J, *factors[layer]) for layer, J in zip(layers, Js)])
     f, io = layer_io_jacobians(model, layers, x)
     outer, dense = [], []
     for layer, (a, D) in zip(layers, io):
@@ -1521,9 +1581,10 @@ def _inf_chunk(model, layers, factors, x, jacobians):
         else:
             raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
                              f"{layer.__class__.__name__}")
-    cov = kron_covariance_outer_inf(outer) if outer else None
+    cov_dense, cov_outer = _inf_calls(f.shape[1])
+    cov = cov_outer(outer) if outer else None
     if dense:
-        conv = kron_covariance_inf(dense)
+        conv = cov_dense(dense)
         cov = conv if cov is None else cov + conv
     return f, cov
 
@@ -1536,7 +1597,9 @@ def glm_predictive_inf(inf, x: Tensor, add=0., multiply=1., layers: Iterable = N
     of `chunk` samples.  `jacobians` as in glm_predictive_efb: "dense" sends output_jacobians'
     rows through kron_covariance_inf; "factored" sends Linear layers through
     kron_covariance_outer_inf and Conv2d layers through kron_covariance_inf on rows formed from
-    the same captures."""
+    the same captures.  Any number of outputs: up to MAX_COV_CLASSES = 32 a chunk goes through
+    these capped calls, above through kron_covariance_inf_tiled / kron_covariance_outer_inf_tiled
+    (64x64 class tiles; bitwise symmetric blocks, chunking changes no bit)."""
     if jacobians not in ("dense", "factored"):
         raise ValueError(f"jacobians must be 'dense' or 'factored', got {jacobians!r}")
     layers = _efb_layers(inf, layers)

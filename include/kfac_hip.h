@@ -714,6 +714,48 @@ KFAC_API int kfac_inf_cov_outer(const kfac_inf_cov_outer_job* jobs, int njobs, i
                                 int accumulate, float* cov, void* workspace, size_t workspace_bytes,
                                 kfac_stream_t stream);
 
+/* ------- GLM predictive covariance under the INF posterior, any number of outputs
+ * The two calls above with the classes tiled instead of capped: the same job structs and
+ * arguments, the same cov (nb x nc x nc contiguous), the same mathematics, nc >= 1 with no cap.
+ * The projections (h | x, t, y) are the capped calls' own launches over all nb*nc rows at once.
+ * A sample's block is then cut into 64x64 class tiles and every tile pair ti >= tj is computed
+ * as two separate fp32 tile Grams,
+ *   part1[c][c'] = sum_k R_b[c][k] * (w_b[k] * R_b[c'][k])   the weight folded into one operand
+ *                                                           as it is loaded; R_b the RAW rows:
+ *       kfac_inf_cov_tiled        R_b = J (stride ldJ), K = nA*nG, w = W
+ *       kfac_inf_cov_outer_tiled  R_b = Delta_b (stride ldD), K = nG, w_b = rho_b
+ *   part2[c][c'] = < y_{b,c}, y_{b,c'} >                     K = r = ra*rg
+ * in ONE Gram launch.  K is cut into 2048-long segments that depend on K alone; a tile is summed
+ * over a segment in fp32 (MFMA, one k-ordered chain from 0 per element); the reduce forms
+ *   sum_jobs ( sum_segments part1 - sum_segments part2 )
+ * in fp64, segments in segment order, jobs in job order, without atomics: the difference of the
+ * two terms is never taken in fp32.  Hence: two calls give identical bits; every block is
+ * bitwise symmetric (the lower triangle is computed and mirrored); a sample's block depends on
+ * that sample only, so chunking the samples changes no bit; padded leading dimensions change no
+ * bit; and with F = 0 kfac_inf_cov_tiled gives the bits of kfac_kron_cov_full_tiled (nt = 1) on
+ * the same J and W with VA, VG identity matrices (one tile body, segmentation and reduce order;
+ * x * 1 and s - 0 are exact).  Against the capped calls (nc <= 32 is valid here: one tile pair)
+ * the segmentation differs (256 against 2048): agreement to fp32 rounding.  The diagonal is not
+ * clamped.  accumulate: cov += the sum, else cov = it.
+ * At most 8 jobs per call; nb*nc must stay below 2^31 - 64, as must the capped calls' column
+ * and row counts (nb*nc*nG and nb*nc*ra dense, nb*(ra+1) outer), the tile pairs and the Gram
+ * launch's task count (nb x (segments of term 1 + of term 2) x tile pairs, summed over the
+ * jobs) must fit 31 bits.  KFAC_EINVAL is returned before any launch, KFAC_EWORKSPACE when the
+ * workspace is smaller than the query's answer.  Workspace per job, in this order, every part
+ * rounded up to 256 bytes, P(K) = nb * ceil(K/2048) * t(t+1)/2 partials of 64x64 floats,
+ * t = ceil(nc/64):
+ *   inf_cov_tiled         X (nb*nc*ra*nG floats), T and Y (nb*nc*r each), P(nA*nG), P(r)
+ *   inf_cov_outer_tiled   HR (nb*(ra+1)*nG floats), T and Y (nb*nc*r each), P(nG), P(r)      */
+KFAC_API size_t kfac_inf_cov_tiled_workspace_bytes(const kfac_inf_cov_job* jobs, int njobs, int64_t nb,
+                                                   int nc);
+KFAC_API int kfac_inf_cov_tiled(const kfac_inf_cov_job* jobs, int njobs, int64_t nb, int nc, int accumulate,
+                                float* cov, void* workspace, size_t workspace_bytes, kfac_stream_t stream);
+KFAC_API size_t kfac_inf_cov_outer_tiled_workspace_bytes(const kfac_inf_cov_outer_job* jobs, int njobs,
+                                                         int64_t nb, int nc);
+KFAC_API int kfac_inf_cov_outer_tiled(const kfac_inf_cov_outer_job* jobs, int njobs, int64_t nb, int nc,
+                                      int accumulate, float* cov, void* workspace, size_t workspace_bytes,
+                                      kfac_stream_t stream);
+
 /* -------------------------------------------------------- posterior samples
  * out_j = (LA_j Z_j LG_j^T)^T, shape (nG x nA): KFAC.sample, curvatures.py:400-405,
  * with Z (nA x nG row-major) supplied by the caller (torch.randn, the reference's
