@@ -128,6 +128,16 @@ class InfCovOuterJob(ctypes.Structure):
                 ("ldW", c_i64), ("F", c_vp), ("ldF", c_i64)]
 
 
+class InfDrawJob(ctypes.Structure):
+    _fields_ = [("rows", InfCovJob), ("C", c_vp), ("Binv", c_vp), ("ldB", c_i64), ("Z", c_vp),
+                ("ldZ", c_i64), ("E", c_vp), ("ldE", c_i64)]
+
+
+class InfDrawOuterJob(ctypes.Structure):
+    _fields_ = [("rows", InfCovOuterJob), ("C", c_vp), ("Binv", c_vp), ("ldB", c_i64), ("Z", c_vp),
+                ("ldZ", c_i64), ("E", c_vp), ("ldE", c_i64)]
+
+
 class SampleJob(ctypes.Structure):
     _fields_ = [("LA", c_vp), ("ldA", c_i64), ("LG", c_vp), ("ldG", c_i64), ("Z", c_vp),
                 ("nA", c_i32), ("nG", c_i32), ("W", c_vp), ("ldW", c_i64), ("bias", c_vp),
@@ -250,6 +260,14 @@ SIGNATURES = {
                                                              c_i64, ctypes.c_int]),
     "kfac_inf_cov_outer": (ctypes.c_int, [ctypes.POINTER(InfCovOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
                                           ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_inf_draws_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(InfDrawJob), ctypes.c_int, c_i64,
+                                                         ctypes.c_int, c_i64]),
+    "kfac_inf_draws": (ctypes.c_int, [ctypes.POINTER(InfDrawJob), ctypes.c_int, c_i64, ctypes.c_int, c_i64,
+                                      ctypes.c_int, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
+    "kfac_inf_draws_outer_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(InfDrawOuterJob), ctypes.c_int,
+                                                               c_i64, ctypes.c_int, c_i64]),
+    "kfac_inf_draws_outer": (ctypes.c_int, [ctypes.POINTER(InfDrawOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
+                                            c_i64, ctypes.c_int, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
     "kfac_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SampleJob), ctypes.c_int]),
     "kfac_sample": (ctypes.c_int, [ctypes.POINTER(SampleJob), ctypes.c_int, ctypes.c_int, c_vp,
                                    ctypes.c_size_t, c_vp]),
@@ -752,6 +770,39 @@ def glm_draws_outer(jobs, nb: int, nc: int, ns: int, out: torch.Tensor, accumula
     check(L.kfac_glm_draws_outer(arr, len(jobs), nb, nc, ns, int(accumulate), ptr(out),
                                  max(out.stride(0), nb * nc), ptr(ws), ws.numel(),
                                  stream_handle(out.device)), "kfac_glm_draws_outer")
+
+
+def inf_draws_workspace_bytes(jobs, nb: int, nc: int, ns: int) -> int:
+    return lib().kfac_inf_draws_workspace_bytes(as_array(InfDrawJob, jobs), len(jobs), nb, nc, ns)
+
+
+def inf_draws_outer_workspace_bytes(jobs, nb: int, nc: int, ns: int) -> int:
+    return lib().kfac_inf_draws_outer_workspace_bytes(as_array(InfDrawOuterJob, jobs), len(jobs), nb, nc, ns)
+
+
+def inf_draws(jobs, nb: int, nc: int, ns: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_inf_draws: out (ns, >= nb*nc) with unit column stride (+)= sum_j [ Z_j (C_j o J_j)^T -
+    Q_j Y_j^T ], the INF posterior's logit draws from Jacobian rows, <= 8 jobs per call."""
+    _draws_out(out, nb, nc, ns, "inf_draws")
+    L = lib()
+    arr = as_array(InfDrawJob, jobs)
+    need = L.kfac_inf_draws_workspace_bytes(arr, len(jobs), nb, nc, ns)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_inf_draws(arr, len(jobs), nb, nc, ns, int(accumulate), ptr(out), max(out.stride(0), nb * nc),
+                           ptr(ws), ws.numel(), stream_handle(out.device)), "kfac_inf_draws")
+
+
+def inf_draws_outer(jobs, nb: int, nc: int, ns: int, out: torch.Tensor, accumulate: bool = False):
+    """kfac_inf_draws_outer: out (ns, >= nb*nc) (+)= sum_j [ abar_b^T (C_j o Z_{j,s}) delta_r -
+    < y_{j,r}, q_{j,s} > ], Linear layers without their Jacobian rows, <= 8 jobs per call."""
+    _draws_out(out, nb, nc, ns, "inf_draws_outer")
+    L = lib()
+    arr = as_array(InfDrawOuterJob, jobs)
+    need = L.kfac_inf_draws_outer_workspace_bytes(arr, len(jobs), nb, nc, ns)
+    ws = workspace.get(out.device, need)
+    check(L.kfac_inf_draws_outer(arr, len(jobs), nb, nc, ns, int(accumulate), ptr(out),
+                                 max(out.stride(0), nb * nc), ptr(ws), ws.numel(),
+                                 stream_handle(out.device)), "kfac_inf_draws_outer")
 
 
 def softmax_mc(mean: torch.Tensor, draws: torch.Tensor, psum: torch.Tensor, hsum: torch.Tensor,

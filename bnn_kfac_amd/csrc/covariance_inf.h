@@ -1,5 +1,6 @@
 // What the capped INF calls (covariance_inf.hip: kfac_inf_cov, kfac_inf_cov_outer) share with
-// the class-tiled ones (covariance_inf_tiled.hip): the argument block of the projection
+// the class-tiled ones (covariance_inf_tiled.hip) and with the INF draw calls
+// (covariance_inf_draws.hip, which also runs them with rows := draws): the argument block of the projection
 // launches h | x, t, y -- which run over all nb*nc rows and know nothing of a class cap --
 // the job checks, the sizes of HX / T / Y, and the launch of the three projections.
 #pragma once

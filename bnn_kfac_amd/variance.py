@@ -1372,9 +1372,9 @@ def _inf_operands(UA: Tensor, UG: Tensor, W: Tensor, F: Tensor):
                             W.data_ptr(), W.numel(), F.data_ptr(), ld(F))
 
 
-def _inf_dense(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
-    """kron_covariance_inf / kron_covariance_inf_tiled: the terms parsed and checked, then
-    `call` per sample chunk (max_classes None: no cap)."""
+def _inf_dense_jobs(terms, who, max_classes):
+    """(tensors to keep alive, kfac_inf_cov_job tuples, nb, nc) of [(J_l, UA_l, UG_l, W_l, F_l)]
+    (max_classes None: no cap)."""
     if not terms:
         raise ValueError("no terms")
     parsed = []
@@ -1395,6 +1395,13 @@ def _inf_dense(terms, who, max_classes, workspace_bytes, call, max_workspace_byt
         held, tail = _inf_operands(UA, UG, W, F)
         keep.extend([J3, *held])
         jobs.append((J3.data_ptr(), ld, nA, nG, *tail))
+    return keep, jobs, nb, nc
+
+
+def _inf_dense(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
+    """kron_covariance_inf / kron_covariance_inf_tiled: the terms parsed and checked, then
+    `call` per sample chunk."""
+    keep, jobs, nb, nc = _inf_dense_jobs(terms, who, max_classes)
     return _run_per_sample(jobs, N.InfCovJob, _cov_job_at, workspace_bytes, call, nb, nc, keep[0].device,
                            max_workspace_bytes)
 
@@ -1438,9 +1445,9 @@ def kron_covariance_inf_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tens
                       N.inf_cov_tiled, max_workspace_bytes)
 
 
-def _inf_outer(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
-    """kron_covariance_outer_inf / kron_covariance_outer_inf_tiled: the terms parsed and
-    checked, then `call` per sample chunk (max_classes None: no cap)."""
+def _inf_outer_jobs(terms, who, max_classes):
+    """(tensors to keep alive, kfac_inf_cov_outer_job tuples, nb, nc) of
+    [(a_l, D_l, UA_l, UG_l, W_l, F_l)] (max_classes None: no cap)."""
     if not terms:
         raise ValueError("no terms")
     parsed = []
@@ -1474,6 +1481,13 @@ def _inf_outer(terms, who, max_classes, workspace_bytes, call, max_workspace_byt
         held, tail = _inf_operands(UA, UG, W, F)
         keep.extend([a2, D3, *held])
         jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0, *tail))
+    return keep, jobs, nb, nc
+
+
+def _inf_outer(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
+    """kron_covariance_outer_inf / kron_covariance_outer_inf_tiled: the terms parsed and
+    checked, then `call` per sample chunk."""
+    keep, jobs, nb, nc = _inf_outer_jobs(terms, who, max_classes)
     return _run_per_sample(jobs, N.InfCovOuterJob, _cov_outer_job_at, workspace_bytes, call, nb, nc,
                            keep[0].device, max_workspace_bytes)
 
@@ -1550,6 +1564,33 @@ def inf_covariance_factors(inf, add=0., multiply=1., layers: Iterable = None):
     numpy.linalg.LinAlgError where s D+ + n is not positive."""
     return {layer: (UA, UG, d.reciprocal().to(torch.float32).contiguous(), (B_inv * sigma[None, :]).contiguous())
             for layer, UA, UG, d, sigma, B_inv in _inf_layer_factors(inf, add, multiply, layers)}
+
+
+def inf_draw_factors(inf, add=0., multiply=1., layers: Iterable = None):
+    """{layer: (UA, UG, W, F, C, Binv)} for kron_draws_inf / kron_draws_outer_inf and
+    inf_posterior_sample: inf_covariance_factors' (UA, UG, W, F), C = sqrt(W) = 1 / sqrt(s D+ + n)
+    formed in fp64 and rounded to fp32 once, and Binv = B^-1 (r, r).  `add` / `multiply` as in
+    inf_covariance_factors; `inf.state` is only read."""
+    return {layer: (UA, UG, d.reciprocal().to(torch.float32).contiguous(), (B_inv * sigma[None, :]).contiguous(),
+                    d.reciprocal().sqrt().to(torch.float32).contiguous(), B_inv.contiguous())
+            for layer, UA, UG, d, sigma, B_inv in _inf_layer_factors(inf, add, multiply, layers)}
+
+
+def inf_posterior_sample(UA: Tensor, UG: Tensor, W: Tensor, F: Tensor, C: Tensor, Binv: Tensor, z: Tensor,
+                         e: Tensor) -> Tensor:
+    """Weight draws x (ns, nA, nG) ~ N(0, P^-1) of one layer's INF posterior, exactly:
+        x = C o z - W o [ UA mat(F^T q) UG^T ] ,   q = F vec(UA^T (C o z) UG) + Binv e ,
+    (UA, UG, W, F, C, Binv) from inf_draw_factors, z (ns, nA, nG) and e (ns, r) standard normal
+    and independent (Matheron's rule on P^-1 = diag(w) - diag(w) U F^T F U^T diag(w); without
+    the e part the covariance lacks a term).  x[s] is in the posterior's (nA, nG) layout: the
+    layer's weight moves by x[s, :cols].T and its bias by x[s, cols].  Plain torch, any device
+    and dtype: the sample the logit draws of kron_draws_inf correspond to, and what INF.sample
+    (the reference's sampler, ported literally) is not."""
+    ns, (ra, rg) = z.shape[0], (UA.shape[1], UG.shape[1])
+    cz = C * z
+    g = (UA.t() @ cz @ UG).reshape(ns, ra * rg)
+    q = g @ F.t() + e @ Binv.t()
+    return cz - W * (UA @ (q @ F).reshape(ns, ra, rg) @ UG.t())
 
 
 def inf_log_det(inf, add=0., multiply=1.) -> Tensor:
@@ -1629,11 +1670,18 @@ def _draw_z(z: Tensor, nA: int, nG: int, ns, index: int):
     return z, (z.stride(0) if z.shape[0] > 1 else nA * nG)
 
 
+def _z_at(zl, s0: int):
+    """The draw fields (Z, ldZ) of a kfac_draw_job from draw s0 on; zl = (z, ldz)."""
+    z, ldz = zl
+    return z.data_ptr() + 4 * s0 * ldz, ldz
+
+
 def _run_draws(jobs, zs, struct, rows_struct, job_at, workspace_bytes, call, nb, nc, device,
-               max_workspace_bytes):
-    """What the two draw calls share: the (ns, nb, nc) result, jobs folded in groups of 8 with
+               max_workspace_bytes, draw_at=_z_at):
+    """What the draw calls share: the (ns, nb, nc) result, jobs folded in groups of 8 with
     `accumulate`, the draws and then the samples halved until a call's scratch fits
-    `max_workspace_bytes` (F[s][r] depends on draw s and row r only: no bit changes)."""
+    `max_workspace_bytes` (F[s][r] depends on draw s and row r only: no bit changes).
+    `draw_at(zs[l], s0)`: the job struct's fields after `rows`, from draw s0 on."""
     ns = zs[0][0].shape[0]
     R = nb * nc
     out = torch.empty(ns, R, dtype=torch.float32, device=device)
@@ -1642,7 +1690,7 @@ def _run_draws(jobs, zs, struct, rows_struct, job_at, workspace_bytes, call, nb,
     groups = [list(zip(jobs[i:i + 8], zs[i:i + 8])) for i in range(0, len(jobs), 8)]
 
     def build(g, b0, s0):
-        return [struct(rows_struct(*job_at(j, b0, nc)), z.data_ptr() + 4 * s0 * ldz, ldz) for j, (z, ldz) in g]
+        return [struct(rows_struct(*job_at(j, b0, nc)), *draw_at(zl, s0)) for j, zl in g]
 
     def need(n, m):
         return max(workspace_bytes(build(g, 0, 0), n, nc, m) for g in groups)
@@ -1706,6 +1754,94 @@ def kron_draws_outer(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]], z: 
                       max_workspace_bytes)
 
 
+# Under the INF posterior a weight draw is x = C o Z - W o [UA mat(F^T q) UG^T],
+# q = F vec(UA^T (C o Z) UG) + Binv eps (inf_posterior_sample), which moves the linearised logits
+# by < M_r o C, Z > - < y_r, q >, y_r = F t_r the covariance calls' projection (kfac_inf_draws,
+# kfac_inf_draws_outer).
+def _inf_draw_at(zl, s0: int):
+    """The fields (C, Binv, ldB, Z, ldZ, E, ldE) of a kfac_inf_draw_job from draw s0 on."""
+    z, ldz, e, lde, C, Binv, ldB = zl
+    return C.data_ptr(), Binv.data_ptr(), ldB, z.data_ptr() + 4 * s0 * ldz, ldz, e.data_ptr() + 4 * s0 * lde, lde
+
+
+def _inf_draw_operands(terms, z, e, who):
+    """(covariance terms, per-term (z, ldz, e, lde, C, Binv, ldB)) after the shape checks of C,
+    Binv, z and e (ValueError before anything touches the device)."""
+    terms = list(terms)
+    if not terms:
+        raise ValueError(f"{who}: no terms")
+    if len(z) != len(terms) or len(e) != len(terms):
+        raise ValueError(f"{who}: {len(terms)} terms, {len(z)} z and {len(e)} e draw tensors")
+    cov_terms, shapes = [], []
+    for *head, UA, UG, W, F, C, Binv in terms:
+        nA, nG, ra, rg = _inf_shapes(UA, UG, W, F)
+        r = ra * rg
+        if tuple(C.shape) != (nA, nG):
+            raise ValueError(f"C {tuple(C.shape)}: expected ({nA}, {nG})")
+        if tuple(Binv.shape) != (r, r):
+            raise ValueError(f"Binv {tuple(Binv.shape)}: expected ({r}, {r})")
+        cov_terms.append((*head, UA, UG, W, F))
+        shapes.append((nA, nG, r))
+    ns = z[0].shape[0] if z[0].dim() == 3 else None
+    for i, (el, (_, _, r)) in enumerate(zip(e, shapes)):
+        if el.dim() != 2 or el.shape[1] != r or (ns is not None and el.shape[0] != ns):
+            raise ValueError(f"e[{i}] {tuple(el.shape)}: expected ({'ns' if ns is None else ns}, {r})")
+    zs = []
+    for i, (zl, el, term, (nA, nG, r)) in enumerate(zip(z, e, terms, shapes)):
+        zc, ldz = _draw_z(zl, nA, nG, ns, i)
+        el = el.detach()
+        N.require_device(el, f"e[{i}]")
+        if el.stride(1) != 1 or (el.shape[0] > 1 and el.stride(0) < r):
+            el = el.contiguous()
+        C, Binv = term[-2].detach().contiguous(), term[-1].detach()
+        N.require_device(C, "C")
+        N.require_device(Binv, "Binv")
+        if Binv.stride(1) != 1 or (r > 1 and Binv.stride(0) < r):
+            Binv = Binv.contiguous()
+        zs.append((zc, ldz, el, el.stride(0) if el.shape[0] > 1 else r, C, Binv, max(Binv.stride(0), r)))
+    return cov_terms, zs
+
+
+def kron_draws_inf(terms: Sequence[Tuple[Tensor, ...]], z: Sequence[Tensor], e: Sequence[Tensor],
+                   max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """Logit draws under the INF posterior from Jacobian rows:
+    F[s, b, c] = sum_l [ < J_l[b, c] o C_l , z_l[s] > - < F_l t_l[b, c] , q_l[s] > ],
+    q_l[s] = F_l vec(UA_l^T (C_l o z_l[s]) UG_l) + Binv_l e_l[s], t as in kron_covariance_inf: what
+    the weight draw inf_posterior_sample(..., z_l[s], e_l[s]) does to the linearised outputs.
+
+    terms: [(J_l, UA_l, UG_l, W_l, F_l, C_l, Binv_l)], J as in kron_covariance_inf, the rest from
+    inf_draw_factors; z[l] (ns, nA_l, nG_l) and e[l] (ns, ra_l*rg_l) fp32 standard normal (a slice
+    along the draws is used in place).  Returns (ns, nb, nc) fp32, any nc.  Two calls give
+    identical bits, and F[s, b, c] depends on sample b's rows and draw s only, so subsets of the
+    samples or of the draws reproduce their entries bit for bit.  More than 8 terms fold in
+    groups of 8; the draws, then the samples, are cut until a call's scratch fits
+    `max_workspace_bytes`.  Shapes are checked (ValueError) before anything touches the device.
+    """
+    cov_terms, zs = _inf_draw_operands(terms, z, e, "kron_draws_inf")
+    keep, jobs, nb, nc = _inf_dense_jobs(cov_terms, "kron_draws_inf", None)
+    return _run_draws(jobs, zs, N.InfDrawJob, N.InfCovJob, _cov_job_at, N.inf_draws_workspace_bytes, N.inf_draws,
+                      nb, nc, keep[0].device, max_workspace_bytes, _inf_draw_at)
+
+
+def kron_draws_outer_inf(terms: Sequence[Tuple[Tensor, ...]], z: Sequence[Tensor], e: Sequence[Tensor],
+                         max_workspace_bytes: int = 1 << 30) -> Tensor:
+    """kron_draws_inf for Linear layers without their Jacobian rows (M[b, c] = [a[b] | 1] D[b, c]^T):
+    F[s, b, c] = sum_l [ abar_l[b]^T (C_l o z_l[s]) D_l[b, c] - < F_l t_l[b, c] , q_l[s] > ].  Per
+    draw 2 nb nA nG flops and one pass over z_l[s] and C_l per 64 samples, plus the projection
+    of the draw itself (2 ra nA nG flops); no weight sample, no forward pass.
+
+    terms: [(a_l, D_l, UA_l, UG_l, W_l, F_l, C_l, Binv_l)], a and D as in
+    kron_covariance_outer_inf; z, e and the guarantees as in kron_draws_inf.  With F = 0 and
+    Binv = 0 the result has the bits of kron_draws_outer on the same a, D with identity factors
+    and z pre-multiplied by C in fp32.
+    """
+    cov_terms, zs = _inf_draw_operands(terms, z, e, "kron_draws_outer_inf")
+    keep, jobs, nb, nc = _inf_outer_jobs(cov_terms, "kron_draws_outer_inf", None)
+    return _run_draws(jobs, zs, N.InfDrawOuterJob, N.InfCovOuterJob, _cov_outer_job_at,
+                      N.inf_draws_outer_workspace_bytes, N.inf_draws_outer, nb, nc, keep[0].device,
+                      max_workspace_bytes, _inf_draw_at)
+
+
 def _softmax_mc_finish(psum: Tensor, hsum: Tensor, ns: int):
     """(probs, expected_entropy, entropy, mutual_information) fp32 from the fp64 sums."""
     probs = psum / ns
@@ -1740,7 +1876,7 @@ class GLMPredictiveMC(NamedTuple):
 def glm_predictive_mc(curv, x: Tensor, n_draws: int = 100, layers: Iterable = None, chunk: int = 64,
                       jacobians: str = "factored", generator: torch.Generator = None,
                       z: Sequence[Tensor] = None, max_draw_bytes: int = 1 << 30,
-                      return_draws: bool = False) -> GLMPredictiveMC:
+                      return_draws: bool = False, add=0., multiply=1.) -> GLMPredictiveMC:
     """The Monte-Carlo GLM predictive of `curv.model`: `n_draws` posterior weight draws applied to
     the linearised network at every x, and the softmax statistics of the resulting logits --
     what `n_draws` x (sample_and_replace() + a forward pass) gives for a network that is linear
@@ -1766,11 +1902,25 @@ def glm_predictive_mc(curv, x: Tensor, n_draws: int = 100, layers: Iterable = No
     chunk holds as many draws as keep the live z within `max_draw_bytes`.  The samples go
     through `chunk` at a time inside each draw chunk, so with more than one draw chunk the
     captures (or Jacobians) of a sample chunk are recomputed per draw chunk; the generator is
-    never replayed.  Chunking either way changes no bit of a draw."""
+    never replayed.  Chunking either way changes no bit of a draw.
+
+    curv may also be an INF: no invert call is needed, the factors come from `inf.state` once per
+    call (inf_draw_factors with `add` / `multiply`, which only INF uses, as glm_predictive_inf
+    takes them), and the draws are exact draws of the INF posterior (inf_posterior_sample's;
+    INF.sample's are not).  "factored" sends Linear layers through kron_draws_outer_inf and Conv2d
+    rows through kron_draws_inf, "dense" output_jacobians' rows through kron_draws_inf.  Per draw
+    chunk and for the layers in order, torch.randn(m, nA, nG, generator=...) and then
+    torch.randn(m, r, generator=...), r the layer's rank; an explicit `z` is a list of per-layer
+    (Z (n_draws, nA, nG), E (n_draws, r)) pairs, sliced and not copied; `max_draw_bytes` counts
+    both."""
     if jacobians not in ("dense", "factored"):
         raise ValueError(f"jacobians must be 'dense' or 'factored', got {jacobians!r}")
     if n_draws < 1:
         raise ValueError(f"n_draws must be at least 1, got {n_draws}")
+    from .curvatures import INF
+    if isinstance(curv, INF):
+        return _glm_mc_inf(curv, x, n_draws, layers, chunk, jacobians, generator, z, max_draw_bytes, return_draws,
+                           add, multiply)
     assert curv.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
     model = curv.model
     efb = hasattr(curv, "eigvecs")
@@ -1826,6 +1976,81 @@ def glm_predictive_mc(curv, x: Tensor, n_draws: int = 100, layers: Iterable = No
             F = kron_draws_outer(outer, zo, lower=not efb) if outer else None
             if dense:
                 rows = kron_draws(dense, zd, lower=not efb)
+                F = rows if F is None else F + rows
+            n, nc = f.shape
+            if psum is None:
+                psum = torch.empty(N_, nc, dtype=torch.float64, device=device)
+                hsum = torch.empty(N_, dtype=torch.float64, device=device)
+                if return_draws:
+                    draws = torch.empty(n_draws, N_, nc, dtype=torch.float32, device=device)
+            if s0 == 0:
+                logits.append(f)
+            N.softmax_mc(f.contiguous(), F, psum[c0:c0 + n], hsum[c0:c0 + n], accumulate=s0 > 0)
+            if return_draws:
+                draws[s0:s0 + m, c0:c0 + n] = F
+        del zc
+    if psum is None:  # no samples
+        raise ValueError("x holds no samples")
+    stats = _softmax_mc_finish(psum, hsum, n_draws)
+    return GLMPredictiveMC(torch.cat(logits), stats[0], stats[2], stats[1], stats[3], draws)
+
+
+def _glm_mc_inf(inf, x, n_draws, layers, chunk, jacobians, generator, z, max_draw_bytes, return_draws, add,
+                multiply):
+    """glm_predictive_mc under an INF posterior (arguments checked there)."""
+    assert inf.state, "State dict is empty. Did you call 'update' prior to this?"
+    model = inf.model
+    layers = _efb_layers(inf, layers)
+    shapes = []
+    for layer in layers:
+        UA, UG = inf.state[layer][0], inf.state[layer][1]
+        shapes.append((UA.shape[0], UG.shape[0], UA.shape[1] * UG.shape[1]))
+    if z is not None:
+        z = [tuple(pair) for pair in z]
+        if len(z) != len(layers):
+            raise ValueError(f"{len(layers)} layers, {len(z)} (Z, E) draw pairs")
+        for i, (pair, (nA, nG, r)) in enumerate(zip(z, shapes)):
+            if len(pair) != 2 or tuple(pair[0].shape) != (n_draws, nA, nG) or tuple(pair[1].shape) != (n_draws, r):
+                got = tuple(tuple(t.shape) for t in pair)
+                raise ValueError(f"z[{i}] {got}: expected a pair ({n_draws}, {nA}, {nG}), ({n_draws}, {r})")
+    factors = inf_draw_factors(inf, add, multiply, layers)
+    per_draw = 4 * sum(nA * nG + r for nA, nG, r in shapes)
+    step = max(1, min(n_draws, max_draw_bytes // max(per_draw, 1)))
+    N_, device = x.shape[0], factors[layers[0]][0].device
+    logits, draws, psum, hsum = [], None, None, None
+    for s0 in range(0, n_draws, step):
+        m = min(step, n_draws - s0)
+        if z is None:
+            zc = []
+            for nA, nG, r in shapes:
+                zl = torch.randn(m, nA, nG, generator=generator, device=device, dtype=torch.float32)
+                zc.append((zl, torch.randn(m, r, generator=generator, device=device, dtype=torch.float32)))
+        else:
+            zc = [(zl[s0:s0 + m], el[s0:s0 + m]) for zl, el in z]
+        for c0 in range(0, N_, chunk):
+            xc = x[c0:c0 + chunk]
+            outer, dense, zo, zd = [], [], [], []
+            if jacobians == "dense":
+                f, Js = output_jacobians(model, layers, xc)
+                dense = [(J, *factors[layer]) for layer, J in zip(layers, Js)]
+                zd = zc
+            else:
+                f, io = layer_io_jacobians(model, layers, xc)
+                for layer, (a, D), zl in zip(layers, io, zc):
+                    if isinstance(layer, torch.nn.Linear):
+                        if a.dim() != 2:
+                            raise ValueError(f"the factored route needs 2-D Linear inputs, got {tuple(a.shape)}")
+                        outer.append((a, D, *factors[layer]))
+                        zo.append(zl)
+                    elif isinstance(layer, torch.nn.Conv2d):
+                        dense.append((_conv_rows(layer, a, D), *factors[layer]))
+                        zd.append(zl)
+                    else:
+                        raise ValueError(f"the factored route handles Linear and Conv2d layers, got "
+                                         f"{layer.__class__.__name__}")
+            F = kron_draws_outer_inf(outer, [p[0] for p in zo], [p[1] for p in zo]) if outer else None
+            if dense:
+                rows = kron_draws_inf(dense, [p[0] for p in zd], [p[1] for p in zd])
                 F = rows if F is None else F + rows
             n, nc = f.shape
             if psum is None:

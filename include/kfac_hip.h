@@ -756,6 +756,90 @@ KFAC_API int kfac_inf_cov_outer_tiled(const kfac_inf_cov_outer_job* jobs, int nj
                                       int accumulate, float* cov, void* workspace, size_t workspace_bytes,
                                       kfac_stream_t stream);
 
+/* ------- GLM Monte-Carlo predictive under the INF posterior: exact logit draws
+ * With P^-1 = diag(w) - diag(w) U F^T F U^T diag(w) as above, c = sqrt(w) entrywise, Z (nA x nG)
+ * and eps (r) standard normal and independent,
+ *   x = c o Z - w o [ UA mat(F^T q) UG^T ] ,   q = F vec(UA^T (c o Z) UG) + B^-1 eps
+ * is distributed N(0, P^-1) exactly (Matheron's rule on the Woodbury form; without the eps part
+ * the covariance lacks a term).  No square root beyond sqrt(w).  The draw moves logit row
+ * r = b*nc + c' of the linearised network by
+ *   F[s][r] (+)= sum_j [ < M_{j,r} o C_j , Z_{j,s} > - < y_{j,r} , q_{j,s} > ] ,   y_r = F t_r ,
+ * t_r, y_r exactly the projections of kfac_inf_cov / kfac_inf_cov_outer.  One draw is one weight
+ * sample for all samples of the call: the draws are jointly consistent.
+ *   kfac_inf_draws        rows given (Conv2d rows, dense Jacobians)
+ *   kfac_inf_draws_outer  Linear layers, M_{b,c'} = abar_b delta_{b,c'}^T, no row is formed: the
+ *                         first term is abar_b^T (C o Z_s) delta_{b,c'}
+ * A job is the covariance call's job plus C (nA*nG floats sqrt(w), flat order i*nG + g; passed,
+ * never computed here), Binv (r x r, row stride ldB), Z (draw s at Z + s*ldZ: nA*nG values in
+ * kfac_sample's order) and E (draw s at E + s*ldE: r values).  Plain numbers: the calls know
+ * nothing of damping.  F[s][r] is at F + s*ldF + r, R = nb*nc, ldF >= R; columns >= R are never
+ * touched.  accumulate: F += the sum over jobs, else F = it.
+ * Stages (fp32 MFMA, exact products, every output element ONE k-ordered chain from 0; products
+ * that are operands are formed as a panel is loaded and never stored):
+ *   y       the covariance calls' own projection launches (h | x, t, y) on the rows, R x r
+ *   F g     the dense projection launches with rows := draws, J := Z, W := C:
+ *           G[s] = F vec(UA^T (C o Z_s) UG), ns x r
+ *   q       Q = G + E Binv^T: the y-launch result G plus ONE second k-ordered chain over r
+ *           (E Binv^T from 0), added once; q_s reads draw s only
+ *   first   outer: one task per (draw, 64-column g-tile, 64-sample tile):
+ *           W[b][g] = sum_a abar_b[a] (C[a][g] Z_s[a][g]) over all of nA (the raw a with the
+ *           implicit ones column; C*Z rounded to fp32 once, as loaded), then
+ *           part[s][g-tile][r] = sum_{g in tile} W[b(r)][g] Delta[r][g], one fma chain in g order
+ *           on the raw Delta (read through a transpose);
+ *           dense: a 64 x 64 tile of Z (C o J)^T over one 2048-long segment of K = nA*nG, the
+ *           raw rows at ldJ scaled by C as they are loaded
+ *   second  a 64 x 64 tile of Q Y^T over one 2048-long segment of r
+ *   reduce  F[s][r] (+)= sum_jobs ( sum_{g-tiles | segments} first - sum_segments second ) in fp64,
+ *           parts in part order, jobs in job order; no atomics; the difference is never taken
+ *           in fp32.  The cut points depend on nA, nG and r alone.
+ * Guarantees: two calls give identical bits; F[s][r] depends on row r's inputs, draw s, the
+ * operands and the job shapes only -- not on nb or ns, nor on where the sample or the draw sits
+ * -- so chunking the samples or the draws changes no bit; pad columns of F are never touched;
+ * with F = 0 and Binv = 0 kfac_inf_draws_outer gives the bits of kfac_glm_draws_outer on the
+ * same a, Delta with identity K1, K2 and Z pre-multiplied by C in fp32 (one tile body, g-tile
+ * cut and reduce order; x * 1 and s - 0 are exact).
+ * At most 8 jobs per call; nc >= 1 and ns >= 1 have no cap; R, ns, the projections' column and
+ * row counts (R*nG and R*ra dense, nb*(ra+1) outer, ns*nG, ns*ra) and every launch's task count
+ * must fit 31 bits.  KFAC_EINVAL: null pointers, pitches below the widths, njobs outside 1..8,
+ * nb, nc or ns < 1, ldF < R; KFAC_EWORKSPACE: a workspace below the query's answer.  All of it
+ * is checked before any launch.  Workspace per job, in this order, every part rounded up to
+ * 256 bytes, T(K) = ceil(K/2048) x ceil(R/64) x ceil(ns/64) tiles of 64x64 floats:
+ *   the rows' HX (R*ra*nG floats dense, nb*(ra+1)*nG outer), T and Y (R*r each); the draws' X
+ *   (ns*ra*nG), T and G (ns*r each); Q (ns*r); outer: Dt (nG*R) and ns x ceil(nG/64) x R floats,
+ *   dense: T(nA*nG); then T(r).                                                           */
+typedef struct kfac_inf_draw_job { /* rows given: Conv2d rows, dense Jacobians */
+  kfac_inf_cov_job rows; /* J, UA, UG, W, F exactly as kfac_inf_cov takes them */
+  const float* C;        /* nA*nG: sqrt(W) entrywise, contiguous */
+  const float* Binv;     /* r x r, row-major */
+  int64_t ldB;
+  const float* Z;        /* draw s at Z + s*ldZ: nA*nG elements, index i*nG + g */
+  int64_t ldZ;
+  const float* E;        /* draw s at E + s*ldE: r elements */
+  int64_t ldE;
+} kfac_inf_draw_job;
+
+typedef struct kfac_inf_draw_outer_job { /* Linear layers, no row formed */
+  kfac_inf_cov_outer_job rows; /* a, D, UA, UG, W, F exactly as kfac_inf_cov_outer takes them */
+  const float* C;
+  const float* Binv;
+  int64_t ldB;
+  const float* Z;
+  int64_t ldZ;
+  const float* E;
+  int64_t ldE;
+} kfac_inf_draw_outer_job;
+
+KFAC_API size_t kfac_inf_draws_workspace_bytes(const kfac_inf_draw_job* jobs, int njobs, int64_t nb, int nc,
+                                               int64_t ns);
+KFAC_API int kfac_inf_draws(const kfac_inf_draw_job* jobs, int njobs, int64_t nb, int nc, int64_t ns,
+                            int accumulate, float* F, int64_t ldF, void* workspace, size_t workspace_bytes,
+                            kfac_stream_t stream);
+KFAC_API size_t kfac_inf_draws_outer_workspace_bytes(const kfac_inf_draw_outer_job* jobs, int njobs, int64_t nb,
+                                                     int nc, int64_t ns);
+KFAC_API int kfac_inf_draws_outer(const kfac_inf_draw_outer_job* jobs, int njobs, int64_t nb, int nc, int64_t ns,
+                                  int accumulate, float* F, int64_t ldF, void* workspace,
+                                  size_t workspace_bytes, kfac_stream_t stream);
+
 /* -------------------------------------------------------- posterior samples
  * out_j = (LA_j Z_j LG_j^T)^T, shape (nG x nA): KFAC.sample, curvatures.py:400-405,
  * with Z (nA x nG row-major) supplied by the caller (torch.randn, the reference's
