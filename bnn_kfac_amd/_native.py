@@ -194,80 +194,10 @@ SIGNATURES = {
                                                         c_i64]),
     "kfac_kron_quadform": (ctypes.c_int, [ctypes.POINTER(QuadJob), ctypes.c_int, c_i64,
                                           ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
-    "kfac_kron_cov_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64,
-                                                        ctypes.c_int]),
-    "kfac_kron_cov": (ctypes.c_int, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64, ctypes.c_int,
-                                     ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
-    "kfac_kron_cov_outer_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovOuterJob), ctypes.c_int,
-                                                              c_i64, ctypes.c_int]),
-    "kfac_kron_cov_outer": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
-                                           ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "kfac_cov_conv_rows": (ctypes.c_int, [ctypes.POINTER(CovConvRowsJob), ctypes.c_int, c_i64, ctypes.c_int,
                                           c_vp]),
-    "kfac_kron_cov_joint_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64,
-                                                              ctypes.c_int]),
-    "kfac_kron_cov_joint": (ctypes.c_int, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64, ctypes.c_int,
-                                           ctypes.c_int, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
-    "kfac_kron_cov_outer_joint_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovOuterJob),
-                                                                    ctypes.c_int, c_i64, ctypes.c_int]),
-    "kfac_kron_cov_outer_joint": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64,
-                                                 ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_vp,
-                                                 ctypes.c_size_t, c_vp]),
-    "kfac_kron_cov_tiled_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64,
-                                                              ctypes.c_int]),
-    "kfac_kron_cov_tiled": (ctypes.c_int, [ctypes.POINTER(CovJob), ctypes.c_int, c_i64, ctypes.c_int,
-                                           ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
-    "kfac_kron_cov_outer_tiled_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovOuterJob),
-                                                                    ctypes.c_int, c_i64, ctypes.c_int]),
-    "kfac_kron_cov_outer_tiled": (ctypes.c_int, [ctypes.POINTER(CovOuterJob), ctypes.c_int, c_i64,
-                                                 ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_size_t,
-                                                 c_vp]),
-    "kfac_glm_draws_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DrawJob), ctypes.c_int, c_i64,
-                                                         ctypes.c_int, c_i64]),
-    "kfac_glm_draws": (ctypes.c_int, [ctypes.POINTER(DrawJob), ctypes.c_int, c_i64, ctypes.c_int, c_i64,
-                                      ctypes.c_int, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
-    "kfac_glm_draws_outer_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DrawOuterJob), ctypes.c_int,
-                                                               c_i64, ctypes.c_int, c_i64]),
-    "kfac_glm_draws_outer": (ctypes.c_int, [ctypes.POINTER(DrawOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
-                                            c_i64, ctypes.c_int, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
     "kfac_softmax_mc": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
                                        c_vp, c_vp, c_vp]),
-    "kfac_kron_cov_sweep_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovSweepJob), ctypes.c_int,
-                                                              c_i64, ctypes.c_int, ctypes.c_int]),
-    "kfac_kron_cov_sweep": (ctypes.c_int, [ctypes.POINTER(CovSweepJob), ctypes.c_int, c_i64, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
-    "kfac_kron_cov_outer_sweep_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovOuterSweepJob),
-                                                                    ctypes.c_int, c_i64, ctypes.c_int,
-                                                                    ctypes.c_int]),
-    "kfac_kron_cov_outer_sweep": (ctypes.c_int, [ctypes.POINTER(CovOuterSweepJob), ctypes.c_int, c_i64,
-                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
-                                                 ctypes.c_size_t, c_vp]),
-    "kfac_kron_cov_full_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovFullJob), ctypes.c_int,
-                                                             c_i64, ctypes.c_int, ctypes.c_int]),
-    "kfac_kron_cov_full": (ctypes.c_int, [ctypes.POINTER(CovFullJob), ctypes.c_int, c_i64, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
-    "kfac_kron_cov_outer_full_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(CovOuterFullJob),
-                                                                   ctypes.c_int, c_i64, ctypes.c_int,
-                                                                   ctypes.c_int]),
-    "kfac_kron_cov_outer_full": (ctypes.c_int, [ctypes.POINTER(CovOuterFullJob), ctypes.c_int, c_i64,
-                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
-                                                ctypes.c_size_t, c_vp]),
-    "kfac_inf_cov_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(InfCovJob), ctypes.c_int, c_i64,
-                                                       ctypes.c_int]),
-    "kfac_inf_cov": (ctypes.c_int, [ctypes.POINTER(InfCovJob), ctypes.c_int, c_i64, ctypes.c_int,
-                                    ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
-    "kfac_inf_cov_outer_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(InfCovOuterJob), ctypes.c_int,
-                                                             c_i64, ctypes.c_int]),
-    "kfac_inf_cov_outer": (ctypes.c_int, [ctypes.POINTER(InfCovOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
-                                          ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
-    "kfac_inf_draws_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(InfDrawJob), ctypes.c_int, c_i64,
-                                                         ctypes.c_int, c_i64]),
-    "kfac_inf_draws": (ctypes.c_int, [ctypes.POINTER(InfDrawJob), ctypes.c_int, c_i64, ctypes.c_int, c_i64,
-                                      ctypes.c_int, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
-    "kfac_inf_draws_outer_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(InfDrawOuterJob), ctypes.c_int,
-                                                               c_i64, ctypes.c_int, c_i64]),
-    "kfac_inf_draws_outer": (ctypes.c_int, [ctypes.POINTER(InfDrawOuterJob), ctypes.c_int, c_i64, ctypes.c_int,
-                                            c_i64, ctypes.c_int, c_vp, c_i64, c_vp, ctypes.c_size_t, c_vp]),
     "kfac_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SampleJob), ctypes.c_int]),
     "kfac_sample": (ctypes.c_int, [ctypes.POINTER(SampleJob), ctypes.c_int, ctypes.c_int, c_vp,
                                    ctypes.c_size_t, c_vp]),
@@ -301,18 +231,84 @@ SIGNATURES = {
     "kfac_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "kfac_version": (ctypes.c_char_p, []),
 }
-# the class-tiled weighted covariance calls: their capped siblings' job structs and arguments
-for _name, _job in (("kfac_kron_cov_full_tiled", CovFullJob), ("kfac_kron_cov_outer_full_tiled", CovOuterFullJob),
-                    ("kfac_kron_cov_sweep_tiled", CovSweepJob),
-                    ("kfac_kron_cov_outer_sweep_tiled", CovOuterSweepJob)):
-    SIGNATURES[_name + "_workspace_bytes"] = (ctypes.c_size_t, [ctypes.POINTER(_job), ctypes.c_int, c_i64,
-                                                                ctypes.c_int, ctypes.c_int])
-    SIGNATURES[_name] = (ctypes.c_int, [ctypes.POINTER(_job), ctypes.c_int, c_i64, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp])
-# the class-tiled INF covariance calls: the capped calls' job structs and arguments
-for _name in ("kfac_inf_cov", "kfac_inf_cov_outer"):
-    SIGNATURES[_name + "_tiled_workspace_bytes"] = SIGNATURES[_name + "_workspace_bytes"]
-    SIGNATURES[_name + "_tiled"] = SIGNATURES[_name]
+# The job-array covariance and draw calls, each described once: (name, job struct, family, doc).
+# Every call is kfac_<name>(jobs, njobs, nb, nc, <family arguments>) with a workspace query
+# kfac_<name>_workspace_bytes(jobs, njobs, nb, nc[, nt | ns]); the SIGNATURES entries are made from
+# this table here, the module-level wrappers <name> and <name>_workspace_bytes further down.
+JOB_CALLS = (
+    ("kron_cov", CovJob, "blocks", "kfac_kron_cov: out (nb, nc, nc) (+)= sum_j T_j T_j^T, <= 8 jobs per call."),
+    ("kron_cov_outer", CovOuterJob, "blocks",
+     "kfac_kron_cov_outer: out (nb, nc, nc) (+)= sum_j s_j V_j V_j^T, <= 8 jobs per call."),
+    ("kron_cov_joint", CovJob, "joint",
+     """kfac_kron_cov_joint: out (nb*nc, >= nb*nc) with unit column stride (+)= sum_j T_j T_j^T
+    over ALL rows of the call, <= 8 jobs per call."""),
+    ("kron_cov_outer_joint", CovOuterJob, "joint",
+     """kfac_kron_cov_outer_joint: out (nb*nc, >= nb*nc) (+)= sum_j S_j[b, b'] W_j[r, r'], <= 8 jobs
+    per call."""),
+    ("kron_cov_tiled", CovJob, "tiled",
+     """kfac_kron_cov_tiled: out (nb, nc, nc) (+)= sum_j T_j T_j^T per sample, any nc, <= 8 jobs
+    per call."""),
+    ("kron_cov_outer_tiled", CovOuterJob, "tiled",
+     """kfac_kron_cov_outer_tiled: out (nb, nc, nc) (+)= sum_j s_j V_j V_j^T per sample, any nc,
+    <= 8 jobs per call."""),
+    ("glm_draws", DrawJob, "draws",
+     """kfac_glm_draws: out (ns, >= nb*nc) with unit column stride (+)= sum_j Z_j T_j^T, <= 8 jobs
+    per call."""),
+    ("glm_draws_outer", DrawOuterJob, "draws",
+     "kfac_glm_draws_outer: out (ns, >= nb*nc) (+)= sum_j u_b^T Z_{j,s} v_r, <= 8 jobs per call."),
+    ("inf_draws", InfDrawJob, "draws",
+     """kfac_inf_draws: out (ns, >= nb*nc) with unit column stride (+)= sum_j [ Z_j (C_j o J_j)^T -
+    Q_j Y_j^T ], the INF posterior's logit draws from Jacobian rows, <= 8 jobs per call."""),
+    ("inf_draws_outer", InfDrawOuterJob, "draws",
+     """kfac_inf_draws_outer: out (ns, >= nb*nc) (+)= sum_j [ abar_b^T (C_j o Z_{j,s}) delta_r -
+    < y_{j,r}, q_{j,s} > ], Linear layers without their Jacobian rows, <= 8 jobs per call."""),
+    ("kron_cov_sweep", CovSweepJob, "weighted",
+     "kfac_kron_cov_sweep: out (nt, nb, nc, nc) (+)= the weighted Grams, <= 8 jobs, nt <= 64."),
+    ("kron_cov_outer_sweep", CovOuterSweepJob, "weighted",
+     "kfac_kron_cov_outer_sweep: out (nt, nb, nc, nc) (+)= the weighted sums, <= 8 jobs, nt <= 64."),
+    ("kron_cov_full", CovFullJob, "weighted",
+     "kfac_kron_cov_full: out (nt, nb, nc, nc) (+)= the per-entry weighted Grams, <= 8 jobs, nt <= 64."),
+    ("kron_cov_outer_full", CovOuterFullJob, "weighted",
+     """kfac_kron_cov_outer_full: out (nt, nb, nc, nc) (+)= Q diag(r) Q^T per grid point, <= 8 jobs,
+    nt <= 64."""),
+    ("kron_cov_sweep_tiled", CovSweepJob, "weighted",
+     "kfac_kron_cov_sweep_tiled: kron_cov_sweep with nc not capped, <= 8 jobs, nt <= 64."),
+    ("kron_cov_outer_sweep_tiled", CovOuterSweepJob, "weighted",
+     "kfac_kron_cov_outer_sweep_tiled: kron_cov_outer_sweep with nc not capped, <= 8 jobs, nt <= 64."),
+    ("kron_cov_full_tiled", CovFullJob, "weighted",
+     "kfac_kron_cov_full_tiled: kron_cov_full with nc not capped, <= 8 jobs, nt <= 64."),
+    ("kron_cov_outer_full_tiled", CovOuterFullJob, "weighted",
+     "kfac_kron_cov_outer_full_tiled: kron_cov_outer_full with nc not capped, <= 8 jobs, nt <= 64."),
+    ("inf_cov", InfCovJob, "blocks",
+     "kfac_inf_cov: out (nb, nc, nc) (+)= sum_j [rows' W-weighted Gram - Gram of F t], <= 8 jobs."),
+    ("inf_cov_outer", InfCovOuterJob, "blocks",
+     """kfac_inf_cov_outer: out (nb, nc, nc) (+)= sum_j [Delta diag(rho) Delta^T - Gram of F t],
+    <= 8 jobs."""),
+    ("inf_cov_tiled", InfCovJob, "tiled", "kfac_inf_cov_tiled: inf_cov for any nc (64x64 class tiles), <= 8 jobs."),
+    ("inf_cov_outer_tiled", InfCovOuterJob, "tiled",
+     "kfac_inf_cov_outer_tiled: inf_cov_outer for any nc (64x64 class tiles), <= 8 jobs."),
+)
+# family -> (the size argument after nc and its C type, whether `out` is followed by its leading
+# dimension ldo); "tiled" is "blocks" in C, the wrappers of the two differ (_blocks_out)
+JOB_CALL_FAMILIES = {"blocks": (None, False), "tiled": (None, False), "weighted": (("nt", ctypes.c_int), False),
+                     "joint": (None, True), "draws": (("ns", c_i64), True)}
+for _name, _job, _family, _ in JOB_CALLS:
+    _size, _ldo = JOB_CALL_FAMILIES[_family]
+    _head = [ctypes.POINTER(_job), ctypes.c_int, c_i64, ctypes.c_int] + ([_size[1]] if _size else [])
+    SIGNATURES[f"kfac_{_name}_workspace_bytes"] = (ctypes.c_size_t, _head)
+    SIGNATURES[f"kfac_{_name}"] = (ctypes.c_int, _head + [ctypes.c_int, c_vp] + ([c_i64] if _ldo else []) +
+                                   [c_vp, ctypes.c_size_t, c_vp])
+
+# C struct name (include/kfac_hip.h) -> its ctypes mirror, every ctypes.Structure above
+STRUCTS = {"kfac_operand": Operand, "kfac_factor_job": FactorJob, "kfac_invert_job": InvertJob,
+           "kfac_eig_job": EigJob, "kfac_quad_job": QuadJob, "kfac_cov_job": CovJob,
+           "kfac_cov_outer_job": CovOuterJob, "kfac_draw_job": DrawJob, "kfac_draw_outer_job": DrawOuterJob,
+           "kfac_cov_conv_rows_job": CovConvRowsJob, "kfac_cov_sweep_job": CovSweepJob,
+           "kfac_cov_outer_sweep_job": CovOuterSweepJob, "kfac_cov_full_job": CovFullJob,
+           "kfac_cov_outer_full_job": CovOuterFullJob, "kfac_inf_cov_job": InfCovJob,
+           "kfac_inf_cov_outer_job": InfCovOuterJob, "kfac_inf_draw_job": InfDrawJob,
+           "kfac_inf_draw_outer_job": InfDrawOuterJob, "kfac_sample_job": SampleJob, "kfac_efb_job": EfbJob,
+           "kfac_gram_job": GramJob, "kfac_tri_job": TriJob}
 
 _lib = None
 _lock = threading.Lock()
@@ -601,34 +597,6 @@ def kron_quadform(jobs, nb: int, abs_sum: bool, out: torch.Tensor):
                                stream_handle(out.device)), "kfac_kron_quadform")
 
 
-def kron_cov_workspace_bytes(jobs, nb: int, nc: int) -> int:
-    return lib().kfac_kron_cov_workspace_bytes(as_array(CovJob, jobs), len(jobs), nb, nc)
-
-
-def kron_cov(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_kron_cov: out (nb, nc, nc) (+)= sum_j T_j T_j^T, <= 8 jobs per call."""
-    L = lib()
-    arr = as_array(CovJob, jobs)
-    need = L.kfac_kron_cov_workspace_bytes(arr, len(jobs), nb, nc)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_kron_cov(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
-                          stream_handle(out.device)), "kfac_kron_cov")
-
-
-def kron_cov_outer_workspace_bytes(jobs, nb: int, nc: int) -> int:
-    return lib().kfac_kron_cov_outer_workspace_bytes(as_array(CovOuterJob, jobs), len(jobs), nb, nc)
-
-
-def kron_cov_outer(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_kron_cov_outer: out (nb, nc, nc) (+)= sum_j s_j V_j V_j^T, <= 8 jobs per call."""
-    L = lib()
-    arr = as_array(CovOuterJob, jobs)
-    need = L.kfac_kron_cov_outer_workspace_bytes(arr, len(jobs), nb, nc)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_kron_cov_outer(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
-                                stream_handle(out.device)), "kfac_kron_cov_outer")
-
-
 def cov_conv_rows_job(x: Operand, D: torch.Tensor, ldD: int, nG: int, M: torch.Tensor, ldM: int) -> CovConvRowsJob:
     """One Conv2d layer of kfac_cov_conv_rows: x the PATCH operand of its input (patch_operand),
     D its output Jacobian with rows (b, c) ldD apart, M the rows to write, ldM apart."""
@@ -646,10 +614,6 @@ def cov_conv_rows(jobs, nb: int, nc: int, device: torch.device = None) -> None:
                                    stream_handle(device)), "kfac_cov_conv_rows")
 
 
-def kron_cov_joint_workspace_bytes(jobs, nb: int, nc: int) -> int:
-    return lib().kfac_kron_cov_joint_workspace_bytes(as_array(CovJob, jobs), len(jobs), nb, nc)
-
-
 def _joint_out(out: torch.Tensor, nb: int, nc: int, what: str):
     """The joint calls write nb*nc rows of nb*nc floats, out.stride(0) apart: refuse a view
     they would write outside of."""
@@ -660,81 +624,12 @@ def _joint_out(out: torch.Tensor, nb: int, nc: int, what: str):
     require_device(out, what)
 
 
-def kron_cov_joint(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_kron_cov_joint: out (nb*nc, >= nb*nc) with unit column stride (+)= sum_j T_j T_j^T
-    over ALL rows of the call, <= 8 jobs per call."""
-    _joint_out(out, nb, nc, "kron_cov_joint")
-    L = lib()
-    arr = as_array(CovJob, jobs)
-    need = L.kfac_kron_cov_joint_workspace_bytes(arr, len(jobs), nb, nc)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_kron_cov_joint(arr, len(jobs), nb, nc, int(accumulate), ptr(out), out.stride(0), ptr(ws),
-                                ws.numel(), stream_handle(out.device)), "kfac_kron_cov_joint")
-
-
-def kron_cov_outer_joint_workspace_bytes(jobs, nb: int, nc: int) -> int:
-    return lib().kfac_kron_cov_outer_joint_workspace_bytes(as_array(CovOuterJob, jobs), len(jobs), nb, nc)
-
-
-def kron_cov_outer_joint(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_kron_cov_outer_joint: out (nb*nc, >= nb*nc) (+)= sum_j S_j[b, b'] W_j[r, r'], <= 8 jobs
-    per call."""
-    _joint_out(out, nb, nc, "kron_cov_outer_joint")
-    L = lib()
-    arr = as_array(CovOuterJob, jobs)
-    need = L.kfac_kron_cov_outer_joint_workspace_bytes(arr, len(jobs), nb, nc)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_kron_cov_outer_joint(arr, len(jobs), nb, nc, int(accumulate), ptr(out), out.stride(0),
-                                      ptr(ws), ws.numel(), stream_handle(out.device)),
-          "kfac_kron_cov_outer_joint")
-
-
 def _blocks_out(out: torch.Tensor, nb: int, nc: int, what: str):
     """The tiled calls write nb contiguous nc x nc blocks: refuse anything else."""
     if tuple(out.shape) != (nb, nc, nc) or not out.is_contiguous():
         raise ValueError(f"{what}: out must be a contiguous ({nb}, {nc}, {nc}) tensor, got "
                          f"{tuple(out.shape)} / {out.stride()}")
     require_device(out, what)
-
-
-def kron_cov_tiled_workspace_bytes(jobs, nb: int, nc: int) -> int:
-    return lib().kfac_kron_cov_tiled_workspace_bytes(as_array(CovJob, jobs), len(jobs), nb, nc)
-
-
-def kron_cov_tiled(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_kron_cov_tiled: out (nb, nc, nc) (+)= sum_j T_j T_j^T per sample, any nc, <= 8 jobs
-    per call."""
-    _blocks_out(out, nb, nc, "kron_cov_tiled")
-    L = lib()
-    arr = as_array(CovJob, jobs)
-    need = L.kfac_kron_cov_tiled_workspace_bytes(arr, len(jobs), nb, nc)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_kron_cov_tiled(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
-                                stream_handle(out.device)), "kfac_kron_cov_tiled")
-
-
-def kron_cov_outer_tiled_workspace_bytes(jobs, nb: int, nc: int) -> int:
-    return lib().kfac_kron_cov_outer_tiled_workspace_bytes(as_array(CovOuterJob, jobs), len(jobs), nb, nc)
-
-
-def kron_cov_outer_tiled(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_kron_cov_outer_tiled: out (nb, nc, nc) (+)= sum_j s_j V_j V_j^T per sample, any nc,
-    <= 8 jobs per call."""
-    _blocks_out(out, nb, nc, "kron_cov_outer_tiled")
-    L = lib()
-    arr = as_array(CovOuterJob, jobs)
-    need = L.kfac_kron_cov_outer_tiled_workspace_bytes(arr, len(jobs), nb, nc)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_kron_cov_outer_tiled(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws),
-                                      ws.numel(), stream_handle(out.device)), "kfac_kron_cov_outer_tiled")
-
-
-def glm_draws_workspace_bytes(jobs, nb: int, nc: int, ns: int) -> int:
-    return lib().kfac_glm_draws_workspace_bytes(as_array(DrawJob, jobs), len(jobs), nb, nc, ns)
-
-
-def glm_draws_outer_workspace_bytes(jobs, nb: int, nc: int, ns: int) -> int:
-    return lib().kfac_glm_draws_outer_workspace_bytes(as_array(DrawOuterJob, jobs), len(jobs), nb, nc, ns)
 
 
 def _draws_out(out: torch.Tensor, nb: int, nc: int, ns: int, what: str):
@@ -748,61 +643,57 @@ def _draws_out(out: torch.Tensor, nb: int, nc: int, ns: int, what: str):
     require_device(out, what)
 
 
-def glm_draws(jobs, nb: int, nc: int, ns: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_glm_draws: out (ns, >= nb*nc) with unit column stride (+)= sum_j Z_j T_j^T, <= 8 jobs
-    per call."""
-    _draws_out(out, nb, nc, ns, "glm_draws")
-    L = lib()
-    arr = as_array(DrawJob, jobs)
-    need = L.kfac_glm_draws_workspace_bytes(arr, len(jobs), nb, nc, ns)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_glm_draws(arr, len(jobs), nb, nc, ns, int(accumulate), ptr(out), max(out.stride(0), nb * nc),
-                           ptr(ws), ws.numel(), stream_handle(out.device)), "kfac_glm_draws")
+def _job_call(name: str, struct, family: str, doc: str):
+    """(workspace query, call) of one JOB_CALLS row: the jobs as a C array, the query, the scratch
+    from the pool, then kfac_<name> on torch's current stream of out's device."""
+    symbol, query_symbol = "kfac_" + name, "kfac_" + name + "_workspace_bytes"
+    out_check = {"tiled": _blocks_out, "joint": _joint_out, "draws": _draws_out}.get(family)
+
+    def query(jobs, *sizes) -> int:
+        return getattr(lib(), query_symbol)(as_array(struct, jobs), len(jobs), *sizes)
+
+    def run(jobs, sizes, out, accumulate):
+        if out_check is not None:
+            out_check(out, *sizes, name)
+        L = lib()
+        arr = as_array(struct, jobs)
+        ws = workspace.get(out.device, getattr(L, query_symbol)(arr, len(jobs), *sizes))
+        ldo = ()
+        if family == "joint":
+            ldo = (out.stride(0),)
+        elif family == "draws":
+            ldo = (max(out.stride(0), sizes[0] * sizes[1]),)
+        check(getattr(L, symbol)(arr, len(jobs), *sizes, int(accumulate), ptr(out), *ldo, ptr(ws), ws.numel(),
+                                 stream_handle(out.device)), symbol)
+
+    # the public signatures, spelled out: (jobs, nb, nc[, nt | ns], out, accumulate=False)
+    if family == "weighted":
+        def workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
+            return query(jobs, nb, nc, nt)
+
+        def call(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
+            run(jobs, (nb, nc, nt), out, accumulate)
+    elif family == "draws":
+        def workspace_bytes(jobs, nb: int, nc: int, ns: int) -> int:
+            return query(jobs, nb, nc, ns)
+
+        def call(jobs, nb: int, nc: int, ns: int, out: torch.Tensor, accumulate: bool = False):
+            run(jobs, (nb, nc, ns), out, accumulate)
+    else:
+        def workspace_bytes(jobs, nb: int, nc: int) -> int:
+            return query(jobs, nb, nc)
+
+        def call(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
+            run(jobs, (nb, nc), out, accumulate)
+    call.__name__ = call.__qualname__ = name
+    workspace_bytes.__name__ = workspace_bytes.__qualname__ = name + "_workspace_bytes"
+    call.__doc__ = doc
+    return workspace_bytes, call
 
 
-def glm_draws_outer(jobs, nb: int, nc: int, ns: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_glm_draws_outer: out (ns, >= nb*nc) (+)= sum_j u_b^T Z_{j,s} v_r, <= 8 jobs per call."""
-    _draws_out(out, nb, nc, ns, "glm_draws_outer")
-    L = lib()
-    arr = as_array(DrawOuterJob, jobs)
-    need = L.kfac_glm_draws_outer_workspace_bytes(arr, len(jobs), nb, nc, ns)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_glm_draws_outer(arr, len(jobs), nb, nc, ns, int(accumulate), ptr(out),
-                                 max(out.stride(0), nb * nc), ptr(ws), ws.numel(),
-                                 stream_handle(out.device)), "kfac_glm_draws_outer")
-
-
-def inf_draws_workspace_bytes(jobs, nb: int, nc: int, ns: int) -> int:
-    return lib().kfac_inf_draws_workspace_bytes(as_array(InfDrawJob, jobs), len(jobs), nb, nc, ns)
-
-
-def inf_draws_outer_workspace_bytes(jobs, nb: int, nc: int, ns: int) -> int:
-    return lib().kfac_inf_draws_outer_workspace_bytes(as_array(InfDrawOuterJob, jobs), len(jobs), nb, nc, ns)
-
-
-def inf_draws(jobs, nb: int, nc: int, ns: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_inf_draws: out (ns, >= nb*nc) with unit column stride (+)= sum_j [ Z_j (C_j o J_j)^T -
-    Q_j Y_j^T ], the INF posterior's logit draws from Jacobian rows, <= 8 jobs per call."""
-    _draws_out(out, nb, nc, ns, "inf_draws")
-    L = lib()
-    arr = as_array(InfDrawJob, jobs)
-    need = L.kfac_inf_draws_workspace_bytes(arr, len(jobs), nb, nc, ns)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_inf_draws(arr, len(jobs), nb, nc, ns, int(accumulate), ptr(out), max(out.stride(0), nb * nc),
-                           ptr(ws), ws.numel(), stream_handle(out.device)), "kfac_inf_draws")
-
-
-def inf_draws_outer(jobs, nb: int, nc: int, ns: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_inf_draws_outer: out (ns, >= nb*nc) (+)= sum_j [ abar_b^T (C_j o Z_{j,s}) delta_r -
-    < y_{j,r}, q_{j,s} > ], Linear layers without their Jacobian rows, <= 8 jobs per call."""
-    _draws_out(out, nb, nc, ns, "inf_draws_outer")
-    L = lib()
-    arr = as_array(InfDrawOuterJob, jobs)
-    need = L.kfac_inf_draws_outer_workspace_bytes(arr, len(jobs), nb, nc, ns)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_inf_draws_outer(arr, len(jobs), nb, nc, ns, int(accumulate), ptr(out),
-                                 max(out.stride(0), nb * nc), ptr(ws), ws.numel(),
-                                 stream_handle(out.device)), "kfac_inf_draws_outer")
+# kron_cov, kron_cov_workspace_bytes, ... inf_cov_outer_tiled, inf_cov_outer_tiled_workspace_bytes
+for _row in JOB_CALLS:
+    globals()[_row[0] + "_workspace_bytes"], globals()[_row[0]] = _job_call(*_row)
 
 
 def softmax_mc(mean: torch.Tensor, draws: torch.Tensor, psum: torch.Tensor, hsum: torch.Tensor,
@@ -827,150 +718,6 @@ def softmax_mc(mean: torch.Tensor, draws: torch.Tensor, psum: torch.Tensor, hsum
     check(lib().kfac_softmax_mc(ptr(mean), mean.stride(0) if nb > 1 else nc, ptr(draws),
                                 draws.stride(0) if ns > 1 else nb * nc, ns, nb, nc, int(accumulate),
                                 ptr(psum), ptr(hsum), stream_handle(mean.device)), "kfac_softmax_mc")
-
-
-def kron_cov_sweep_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
-    return lib().kfac_kron_cov_sweep_workspace_bytes(as_array(CovSweepJob, jobs), len(jobs), nb, nc, nt)
-
-
-def kron_cov_sweep(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_kron_cov_sweep: out (nt, nb, nc, nc) (+)= the weighted Grams, <= 8 jobs, nt <= 64."""
-    L = lib()
-    arr = as_array(CovSweepJob, jobs)
-    need = L.kfac_kron_cov_sweep_workspace_bytes(arr, len(jobs), nb, nc, nt)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_kron_cov_sweep(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws), ws.numel(),
-                                stream_handle(out.device)), "kfac_kron_cov_sweep")
-
-
-def kron_cov_outer_sweep_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
-    return lib().kfac_kron_cov_outer_sweep_workspace_bytes(as_array(CovOuterSweepJob, jobs), len(jobs),
-                                                           nb, nc, nt)
-
-
-def kron_cov_outer_sweep(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_kron_cov_outer_sweep: out (nt, nb, nc, nc) (+)= the weighted sums, <= 8 jobs, nt <= 64."""
-    L = lib()
-    arr = as_array(CovOuterSweepJob, jobs)
-    need = L.kfac_kron_cov_outer_sweep_workspace_bytes(arr, len(jobs), nb, nc, nt)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_kron_cov_outer_sweep(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws),
-                                      ws.numel(), stream_handle(out.device)), "kfac_kron_cov_outer_sweep")
-
-
-def kron_cov_full_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
-    return lib().kfac_kron_cov_full_workspace_bytes(as_array(CovFullJob, jobs), len(jobs), nb, nc, nt)
-
-
-def kron_cov_full(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_kron_cov_full: out (nt, nb, nc, nc) (+)= the per-entry weighted Grams, <= 8 jobs, nt <= 64."""
-    L = lib()
-    arr = as_array(CovFullJob, jobs)
-    need = L.kfac_kron_cov_full_workspace_bytes(arr, len(jobs), nb, nc, nt)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_kron_cov_full(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws), ws.numel(),
-                               stream_handle(out.device)), "kfac_kron_cov_full")
-
-
-def kron_cov_outer_full_workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
-    return lib().kfac_kron_cov_outer_full_workspace_bytes(as_array(CovOuterFullJob, jobs), len(jobs),
-                                                          nb, nc, nt)
-
-
-def kron_cov_outer_full(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_kron_cov_outer_full: out (nt, nb, nc, nc) (+)= Q diag(r) Q^T per grid point, <= 8 jobs,
-    nt <= 64."""
-    L = lib()
-    arr = as_array(CovOuterFullJob, jobs)
-    need = L.kfac_kron_cov_outer_full_workspace_bytes(arr, len(jobs), nb, nc, nt)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_kron_cov_outer_full(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws),
-                                     ws.numel(), stream_handle(out.device)), "kfac_kron_cov_outer_full")
-
-
-def _weighted_tiled(name: str, struct):
-    """(workspace query, call) of the class-tiled weighted covariance call `name`: the capped
-    sibling's job struct and (nt, nb, nc, nc) output, nc not capped, <= 8 jobs, nt <= 64."""
-    def workspace_bytes(jobs, nb: int, nc: int, nt: int) -> int:
-        return getattr(lib(), name + "_workspace_bytes")(as_array(struct, jobs), len(jobs), nb, nc, nt)
-
-    def call(jobs, nb: int, nc: int, nt: int, out: torch.Tensor, accumulate: bool = False):
-        L = lib()
-        arr = as_array(struct, jobs)
-        need = getattr(L, name + "_workspace_bytes")(arr, len(jobs), nb, nc, nt)
-        ws = workspace.get(out.device, need)
-        check(getattr(L, name)(arr, len(jobs), nb, nc, nt, int(accumulate), ptr(out), ptr(ws), ws.numel(),
-                               stream_handle(out.device)), name)
-
-    return workspace_bytes, call
-
-
-kron_cov_full_tiled_workspace_bytes, kron_cov_full_tiled = _weighted_tiled("kfac_kron_cov_full_tiled", CovFullJob)
-kron_cov_outer_full_tiled_workspace_bytes, kron_cov_outer_full_tiled = _weighted_tiled(
-    "kfac_kron_cov_outer_full_tiled", CovOuterFullJob)
-kron_cov_sweep_tiled_workspace_bytes, kron_cov_sweep_tiled = _weighted_tiled("kfac_kron_cov_sweep_tiled",
-                                                                             CovSweepJob)
-kron_cov_outer_sweep_tiled_workspace_bytes, kron_cov_outer_sweep_tiled = _weighted_tiled(
-    "kfac_kron_cov_outer_sweep_tiled", CovOuterSweepJob)
-
-
-def inf_cov_workspace_bytes(jobs, nb: int, nc: int) -> int:
-    return lib().kfac_inf_cov_workspace_bytes(as_array(InfCovJob, jobs), len(jobs), nb, nc)
-
-
-def inf_cov(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_inf_cov: out (nb, nc, nc) (+)= sum_j [rows' W-weighted Gram - Gram of F t], <= 8 jobs."""
-    L = lib()
-    arr = as_array(InfCovJob, jobs)
-    need = L.kfac_inf_cov_workspace_bytes(arr, len(jobs), nb, nc)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_inf_cov(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
-                         stream_handle(out.device)), "kfac_inf_cov")
-
-
-def inf_cov_outer_workspace_bytes(jobs, nb: int, nc: int) -> int:
-    return lib().kfac_inf_cov_outer_workspace_bytes(as_array(InfCovOuterJob, jobs), len(jobs), nb, nc)
-
-
-def inf_cov_outer(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_inf_cov_outer: out (nb, nc, nc) (+)= sum_j [Delta diag(rho) Delta^T - Gram of F t],
-    <= 8 jobs."""
-    L = lib()
-    arr = as_array(InfCovOuterJob, jobs)
-    need = L.kfac_inf_cov_outer_workspace_bytes(arr, len(jobs), nb, nc)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_inf_cov_outer(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
-                               stream_handle(out.device)), "kfac_inf_cov_outer")
-
-
-def inf_cov_tiled_workspace_bytes(jobs, nb: int, nc: int) -> int:
-    return lib().kfac_inf_cov_tiled_workspace_bytes(as_array(InfCovJob, jobs), len(jobs), nb, nc)
-
-
-def inf_cov_tiled(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_inf_cov_tiled: inf_cov for any nc (64x64 class tiles), <= 8 jobs."""
-    _blocks_out(out, nb, nc, "inf_cov_tiled")
-    L = lib()
-    arr = as_array(InfCovJob, jobs)
-    need = L.kfac_inf_cov_tiled_workspace_bytes(arr, len(jobs), nb, nc)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_inf_cov_tiled(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
-                               stream_handle(out.device)), "kfac_inf_cov_tiled")
-
-
-def inf_cov_outer_tiled_workspace_bytes(jobs, nb: int, nc: int) -> int:
-    return lib().kfac_inf_cov_outer_tiled_workspace_bytes(as_array(InfCovOuterJob, jobs), len(jobs), nb, nc)
-
-
-def inf_cov_outer_tiled(jobs, nb: int, nc: int, out: torch.Tensor, accumulate: bool = False):
-    """kfac_inf_cov_outer_tiled: inf_cov_outer for any nc (64x64 class tiles), <= 8 jobs."""
-    _blocks_out(out, nb, nc, "inf_cov_outer_tiled")
-    L = lib()
-    arr = as_array(InfCovOuterJob, jobs)
-    need = L.kfac_inf_cov_outer_tiled_workspace_bytes(arr, len(jobs), nb, nc)
-    ws = workspace.get(out.device, need)
-    check(L.kfac_inf_cov_outer_tiled(arr, len(jobs), nb, nc, int(accumulate), ptr(out), ptr(ws), ws.numel(),
-                                     stream_handle(out.device)), "kfac_inf_cov_outer_tiled")
 
 
 def sample(jobs, device: torch.device, accumulate: bool) -> None:

@@ -237,31 +237,102 @@ def _cov_rows(J: Tensor, K: int):
     return J, ld
 
 
-def _cov_jobs(terms, lower: bool, who: str, max_classes: int = None):
-    """(tensors to keep alive, kfac_cov_job tuples, nb, nc) of [(J_l, K1_l, K2_l)]."""
+def _rows_head(J: Tensor, nA: int, nG: int):
+    """The head of a term given by its Jacobian rows J, (nb, nc, nA*nG) or (nc, nA*nG).  The shape
+    phase happens here (_cov_rows); returns (nb, nc, None, fields), `fields(keep)` the device
+    phase: the job tuple's first four fields (J, ldJ, nA, nG), J joining `keep`."""
+    J3, ld = _cov_rows(J, nA * nG)
+
+    def fields(keep):
+        N.require_device(J3, "J")
+        keep.append(J3)
+        return J3.data_ptr(), ld, nA, nG
+
+    return J3.shape[0], J3.shape[1], None, fields
+
+
+def _outer_head(a: Tensor, D: Tensor, nA: int, nG: int, factor: str, F: Tensor):
+    """The head of a Linear layer's term given by (a, D) in place of its rows: a (nb, cols) or
+    (cols,), D (nb, nc, nG) or (nc, nG), nA = cols + 1 (the ones column is implicit) or cols;
+    `factor`, `F`: name and tensor of the A-side factor, for the message.  The shape phase
+    happens here; returns (nb, nc, a's rows, fields), `fields(keep)` the device phase: the job
+    tuple's first eight fields (a, lda, cols, has_ones, D, ldD, nG, 0), a (copied unless its rows
+    have unit stride and do not overlap) and D joining `keep`."""
+    D3, ldD = _cov_rows(D, nG)
+    a2 = a.detach()
+    a2 = a2.reshape(1, -1) if a2.dim() == 1 else a2
+    if a2.dim() != 2:
+        raise ValueError(f"a {tuple(a2.shape)}: expected (nb, cols), a Linear layer's 2-D input")
+    cols = a2.shape[1]
+    if nA not in (cols, cols + 1) or cols == 0:
+        raise ValueError(f"a has {cols} columns, {factor} {tuple(F.shape)} needs {nA} or {nA - 1}")
+    nb = D3.shape[0]
+
+    def fields(keep):
+        ac = a2.contiguous() if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols) else a2
+        lda = ac.stride(0) if nb > 1 else cols
+        for t, what in ((ac, "a"), (D3, "D")):
+            N.require_device(t, what)
+        keep.extend([ac, D3])
+        return ac.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0
+
+    return nb, D3.shape[1], a2.shape[0], fields
+
+
+def _parse_terms(terms, shapes, who: str, max_classes, weights: str = None):
+    """The term loop every builder shares, shapes only (nothing touches the device):
+    `shapes(term)` -> (head (_rows_head / _outer_head), what the device phase needs of the tail,
+    the grid sizes of the tail's weights).  Establishes the common (nb, nc) and, for the weighted
+    calls, nt (`weights`: what nt counts, for the message); `max_classes` None: no cap on nc.
+    Returns ([(the head's device phase, tail)], nb, nc, nt)."""
     if not terms:
         raise ValueError("no terms")
-    keep, jobs = [], []
-    nb = nc = None
-    for J, K1, K2 in terms:
+    parsed = []
+    nb = nc = nt = None
+    for term in terms:
+        (tnb, tnc, a_rows, fields), tail, counts = shapes(term)
+        if nb is None:
+            nb, nc, nt = tnb, tnc, counts[0] if counts else None
+        elif (tnb, tnc) != (nb, nc):
+            raise ValueError("all terms need the same (nb, nc)")
+        if a_rows is not None and a_rows != nb:
+            raise ValueError(f"a has {a_rows} rows, D has {nb} samples")
+        if counts and (nt == 0 or counts.count(nt) != len(counts)):
+            raise ValueError(f"all weights need the same number nt >= 1 of {weights}")
+        if max_classes is not None and nc > max_classes:
+            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
+        parsed.append((fields, tail))
+    return parsed, nb, nc, nt
+
+
+def _kron_jobs(terms, outer: bool, lower: bool, who: str, max_classes):
+    """_cov_jobs (outer False) / _cov_outer_jobs (outer True)."""
+    def shapes(term):
+        if outer:
+            a, D, K1, K2 = term
+        else:
+            J, K1, K2 = term
         if K1.dim() != 2 or K2.dim() != 2 or K1.shape[0] != K1.shape[1] or K2.shape[0] != K2.shape[1]:
             raise ValueError(f"K1 {tuple(K1.shape)} / K2 {tuple(K2.shape)}: expected square matrices")
         nA, nG = K1.shape[0], K2.shape[0]
-        J3, ld = _cov_rows(J, nA * nG)
-        if nb is None:
-            nb, nc = J3.shape[0], J3.shape[1]
-        elif (J3.shape[0], J3.shape[1]) != (nb, nc):
-            raise ValueError("all terms need the same (nb, nc)")
-        if max_classes is not None and nc > max_classes:
-            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
-        for t, what in ((J3, "J"), (K1, "K1"), (K2, "K2")):
+        return (_outer_head(a, D, nA, nG, "K1", K1) if outer else _rows_head(J, nA, nG)), (K1, K2), ()
+
+    parsed, nb, nc, _ = _parse_terms(terms, shapes, who, max_classes)
+    keep, jobs = [], []
+    for head, (K1, K2) in parsed:
+        fields = head(keep)
+        for t, what in ((K1, "K1"), (K2, "K2")):
             N.require_device(t, what)
         K1c = K1.detach() if K1.stride(-1) == 1 else K1.detach().contiguous()
         K2c = K2.detach() if K2.stride(-1) == 1 else K2.detach().contiguous()
-        keep.extend([J3, K1c, K2c])
-        jobs.append((J3.data_ptr(), ld, nA, nG, K1c.data_ptr(), K1c.stride(0), K2c.data_ptr(),
-                     K2c.stride(0), int(lower), int(lower)))
+        keep.extend([K1c, K2c])
+        jobs.append((*fields, K1c.data_ptr(), K1c.stride(0), K2c.data_ptr(), K2c.stride(0), int(lower), int(lower)))
     return keep, jobs, nb, nc
+
+
+def _cov_jobs(terms, lower: bool, who: str, max_classes: int = None):
+    """(tensors to keep alive, kfac_cov_job tuples, nb, nc) of [(J_l, K1_l, K2_l)]."""
+    return _kron_jobs(terms, False, lower, who, max_classes)
 
 
 def _cov_job_at(j, b0: int, nc: int):
@@ -303,7 +374,8 @@ def kron_covariance(terms: Sequence[Tuple[Tensor, Tensor, Tensor]], lower: bool 
     (KFAC.invert's Cholesky factors).  Returns (nb, nc, nc) fp32, every block bitwise
     symmetric.  More than 8 terms fold in groups of 8; the samples are cut into chunks
     that need at most `max_workspace_bytes` of scratch each (a sample's block depends
-    on that sample only, so chunking does not change a bit).
+    on that sample only, so chunking does not change a bit).  Shapes are checked
+    (ValueError) before anything touches the device.
     """
     keep, jobs, nb, nc = _cov_jobs(terms, lower, "kron_covariance", MAX_COV_CLASSES)
     return _run_per_sample(jobs, N.CovJob, _cov_job_at, N.kron_cov_workspace_bytes, N.kron_cov, nb, nc,
@@ -485,41 +557,7 @@ def _conv_rows(layer: torch.nn.Conv2d, a: Tensor, D: Tensor) -> Tensor:
 
 def _cov_outer_jobs(terms, lower: bool, who: str, max_classes: int = None):
     """(tensors to keep alive, kfac_cov_outer_job tuples, nb, nc) of [(a_l, D_l, K1_l, K2_l)]."""
-    if not terms:
-        raise ValueError("no terms")
-    keep, jobs = [], []
-    nb = nc = None
-    for a, D, K1, K2 in terms:
-        if K1.dim() != 2 or K2.dim() != 2 or K1.shape[0] != K1.shape[1] or K2.shape[0] != K2.shape[1]:
-            raise ValueError(f"K1 {tuple(K1.shape)} / K2 {tuple(K2.shape)}: expected square matrices")
-        nA, nG = K1.shape[0], K2.shape[0]
-        D3, ldD = _cov_rows(D, nG)
-        a2 = a.detach()
-        a2 = a2.reshape(1, -1) if a2.dim() == 1 else a2
-        if a2.dim() != 2:
-            raise ValueError(f"a {tuple(a2.shape)}: expected (nb, cols), a Linear layer's 2-D input")
-        cols = a2.shape[1]
-        if nA not in (cols, cols + 1) or cols == 0:
-            raise ValueError(f"a has {cols} columns, K1 {tuple(K1.shape)} needs {nA} or {nA - 1}")
-        if nb is None:
-            nb, nc = D3.shape[0], D3.shape[1]
-        elif (D3.shape[0], D3.shape[1]) != (nb, nc):
-            raise ValueError("all terms need the same (nb, nc)")
-        if a2.shape[0] != nb:
-            raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
-        if max_classes is not None and nc > max_classes:
-            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
-        if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols):
-            a2 = a2.contiguous()
-        lda = a2.stride(0) if nb > 1 else cols
-        for t, what in ((a2, "a"), (D3, "D"), (K1, "K1"), (K2, "K2")):
-            N.require_device(t, what)
-        K1c = K1.detach() if K1.stride(-1) == 1 else K1.detach().contiguous()
-        K2c = K2.detach() if K2.stride(-1) == 1 else K2.detach().contiguous()
-        keep.extend([a2, D3, K1c, K2c])
-        jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0,
-                     K1c.data_ptr(), K1c.stride(0), K2c.data_ptr(), K2c.stride(0), int(lower), int(lower)))
-    return keep, jobs, nb, nc
+    return _kron_jobs(terms, True, lower, who, max_classes)
 
 
 def _cov_outer_job_at(j, b0: int, nc: int):
@@ -764,22 +802,33 @@ def _damping_grid(dampings, count: int):
     return grid
 
 
-def _sweep_weights(w: Tensor, n: int, what: str):
-    """(w as (nt, n) with unit column stride, its row stride)."""
+def _sweep_weight_rows(w: Tensor, n: int, what: str):
+    """w as (nt, n): the shape check, which needs no device."""
     w = w.detach()
     if w.dim() == 1:
         w = w.unsqueeze(0)
     if w.dim() != 2 or w.shape[1] != n:
         raise ValueError(f"{what} {tuple(w.shape)}: expected (nt, {n})")
+    return w
+
+
+def _sweep_weights(w: Tensor, n: int, what: str):
+    """(w (nt, n) of _sweep_weight_rows with unit column stride, its row stride)."""
     N.require_device(w, what)
     if w.stride(1) != 1 or (w.shape[0] > 1 and w.stride(0) < n):
         w = w.contiguous()
     return w, (w.stride(0) if w.shape[0] > 1 else n)
 
 
-def _sweep_basis(V: Tensor, what: str):
+def _square(V: Tensor, what: str) -> int:
+    """The order of a square matrix of eigenvectors: the shape check, which needs no device."""
     if V.dim() != 2 or V.shape[0] != V.shape[1]:
         raise ValueError(f"{what} {tuple(V.shape)}: expected a square matrix of eigenvectors")
+    return V.shape[0]
+
+
+def _sweep_basis(V: Tensor, what: str):
+    """(V, square by _square, with unit column stride, its row stride)."""
     N.require_device(V, what)
     V = V.detach() if V.stride(-1) == 1 else V.detach().contiguous()
     return V, max(V.stride(0), V.shape[0])
@@ -818,39 +867,53 @@ def _run_sweep(build, workspace_bytes, call, njobs, nb, nc, nt, device, max_work
     return out
 
 
-def _sweep_dense(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
-    """kron_covariance_sweep / kron_covariance_sweep_tiled: the terms parsed and checked, then
-    `call` through _run_sweep; `max_classes` None: no cap on nc."""
-    if not terms:
-        raise ValueError("no terms")
-    keep, jobs = [], []
-    nb = nc = nt = None
-    for J, VA, VG, wA, wG in terms:
-        VAc, ldA = _sweep_basis(VA, "VA")
-        VGc, ldG = _sweep_basis(VG, "VG")
-        nA, nG = VAc.shape[0], VGc.shape[0]
-        J3, ld = _cov_rows(J, nA * nG)
-        N.require_device(J3, "J")
-        wAc, ldwA = _sweep_weights(wA, nA, "wA")
-        wGc, ldwG = _sweep_weights(wG, nG, "wG")
-        if nb is None:
-            nb, nc, nt = J3.shape[0], J3.shape[1], wAc.shape[0]
-        elif (J3.shape[0], J3.shape[1]) != (nb, nc):
-            raise ValueError("all terms need the same (nb, nc)")
-        if wAc.shape[0] != nt or wGc.shape[0] != nt or nt == 0:
-            raise ValueError("all weights need the same number nt >= 1 of rows")
-        if max_classes is not None and nc > max_classes:
-            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
-        keep.extend([J3, VAc, VGc, wAc, wGc])
-        jobs.append((J3.data_ptr(), ld, nA, nG, VAc.data_ptr(), ldA, VGc.data_ptr(), ldG,
-                     wAc.data_ptr(), ldwA, wGc.data_ptr(), ldwG))
+def _weighted(parse, struct, terms, outer: bool, who: str, max_classes, workspace_bytes, call,
+              max_workspace_bytes):
+    """What the eight weighted calls share: the terms parsed and checked by `parse`
+    (_sweep_jobs / _full_jobs), then `call` through _run_sweep; `max_classes` None: no cap."""
+    keep, jobs, nb, nc, nt = parse(terms, outer, who, max_classes)
+    job_at = _cov_outer_job_at if outer else _cov_job_at
 
     def build(i, b0, t0):
-        j = jobs[i]
-        return N.CovSweepJob(j[0] + 4 * b0 * nc * j[1], *j[1:8], j[8] + 4 * t0 * j[9], j[9],
-                             j[10] + 4 * t0 * j[11], j[11])
+        # the head moves to sample b0, the weights' (pointer, row stride) pairs to grid point t0
+        fixed, weights = jobs[i]
+        if len(weights) == 1:
+            (W, ldW), = weights
+            return struct(*job_at(fixed, b0, nc), W + 4 * t0 * ldW, ldW)
+        (wA, ldwA), (wG, ldwG) = weights
+        return struct(*job_at(fixed, b0, nc), wA + 4 * t0 * ldwA, ldwA, wG + 4 * t0 * ldwG, ldwG)
 
     return _run_sweep(build, workspace_bytes, call, len(jobs), nb, nc, nt, keep[0].device, max_workspace_bytes)
+
+
+def _sweep_jobs(terms, outer: bool, who: str, max_classes):
+    """(tensors to keep alive, per term (the job tuple up to ldG, [(wA, ldwA), (wG, ldwG)]), nb,
+    nc, nt) of [(J_l, VA_l, VG_l, wA_l, wG_l)] or, outer, [(a_l, D_l, VA_l, VG_l, wA_l, wG_l)]."""
+    def shapes(term):
+        if outer:
+            a, D, VA, VG, wA, wG = term
+        else:
+            J, VA, VG, wA, wG = term
+        nA, nG = _square(VA, "VA"), _square(VG, "VG")
+        head = _outer_head(a, D, nA, nG, "VA", VA) if outer else _rows_head(J, nA, nG)
+        wA, wG = _sweep_weight_rows(wA, nA, "wA"), _sweep_weight_rows(wG, nG, "wG")
+        return head, (VA, VG, wA, wG), (wA.shape[0], wG.shape[0])
+
+    parsed, nb, nc, nt = _parse_terms(terms, shapes, who, max_classes, "rows")
+    keep, jobs = [], []
+    for head, (VA, VG, wA, wG) in parsed:
+        VAc, ldA = _sweep_basis(VA, "VA")
+        VGc, ldG = _sweep_basis(VG, "VG")
+        if not outer:
+            fields = head(keep)
+        wAc, ldwA = _sweep_weights(wA, VAc.shape[0], "wA")
+        wGc, ldwG = _sweep_weights(wG, VGc.shape[0], "wG")
+        if outer:  # (a and D have always been looked at after the weights here)
+            fields = head(keep)
+        keep.extend([VAc, VGc, wAc, wGc])
+        jobs.append(((*fields, VAc.data_ptr(), ldA, VGc.data_ptr(), ldG),
+                     ((wAc.data_ptr(), ldwA), (wGc.data_ptr(), ldwG))))
+    return keep, jobs, nb, nc, nt
 
 
 def kron_covariance_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
@@ -862,10 +925,11 @@ def kron_covariance_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, 
     terms: [(J_l, VA_l, VG_l, wA_l, wG_l)], J as kron_covariance takes it, VA (nA x nA) /
     VG (nG x nG) eigenvectors as columns, wA (nt, nA) / wG (nt, nG) non-negative weights
     (damping_weights).  Returns (nt, nb, nc, nc) fp32; per grid point kron_covariance's
-    guarantees hold, and slice t has the bits of the call with row t's weights alone.
+    guarantees hold, and slice t has the bits of the call with row t's weights alone.  Shapes are
+    checked (ValueError) before anything touches the device.
     """
-    return _sweep_dense(terms, "kron_covariance_sweep", MAX_COV_CLASSES, N.kron_cov_sweep_workspace_bytes,
-                        N.kron_cov_sweep, max_workspace_bytes)
+    return _weighted(_sweep_jobs, N.CovSweepJob, terms, False, "kron_covariance_sweep", MAX_COV_CLASSES,
+                     N.kron_cov_sweep_workspace_bytes, N.kron_cov_sweep, max_workspace_bytes)
 
 
 def kron_covariance_sweep_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
@@ -876,55 +940,8 @@ def kron_covariance_sweep_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Te
     are kron_covariance_sweep's; with every weight 1 slice t has the bits of
     kron_covariance_tiled(lower=False) on the same rows; against kron_covariance_sweep
     (nc <= 32, another summation order) it agrees to fp32 rounding."""
-    return _sweep_dense(terms, "kron_covariance_sweep_tiled", None, N.kron_cov_sweep_tiled_workspace_bytes,
-                        N.kron_cov_sweep_tiled, max_workspace_bytes)
-
-
-def _sweep_outer(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
-    """kron_covariance_outer_sweep / kron_covariance_outer_sweep_tiled: as _sweep_dense."""
-    if not terms:
-        raise ValueError("no terms")
-    keep, jobs = [], []
-    nb = nc = nt = None
-    for a, D, VA, VG, wA, wG in terms:
-        VAc, ldA = _sweep_basis(VA, "VA")
-        VGc, ldG = _sweep_basis(VG, "VG")
-        nA, nG = VAc.shape[0], VGc.shape[0]
-        D3, ldD = _cov_rows(D, nG)
-        a2 = a.detach()
-        a2 = a2.reshape(1, -1) if a2.dim() == 1 else a2
-        if a2.dim() != 2:
-            raise ValueError(f"a {tuple(a2.shape)}: expected (nb, cols), a Linear layer's 2-D input")
-        cols = a2.shape[1]
-        if nA not in (cols, cols + 1) or cols == 0:
-            raise ValueError(f"a has {cols} columns, VA {tuple(VA.shape)} needs {nA} or {nA - 1}")
-        wAc, ldwA = _sweep_weights(wA, nA, "wA")
-        wGc, ldwG = _sweep_weights(wG, nG, "wG")
-        if nb is None:
-            nb, nc, nt = D3.shape[0], D3.shape[1], wAc.shape[0]
-        elif (D3.shape[0], D3.shape[1]) != (nb, nc):
-            raise ValueError("all terms need the same (nb, nc)")
-        if a2.shape[0] != nb:
-            raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
-        if wAc.shape[0] != nt or wGc.shape[0] != nt or nt == 0:
-            raise ValueError("all weights need the same number nt >= 1 of rows")
-        if max_classes is not None and nc > max_classes:
-            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
-        if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols):
-            a2 = a2.contiguous()
-        lda = a2.stride(0) if nb > 1 else cols
-        for t, what in ((a2, "a"), (D3, "D")):
-            N.require_device(t, what)
-        keep.extend([a2, D3, VAc, VGc, wAc, wGc])
-        jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0,
-                     VAc.data_ptr(), ldA, VGc.data_ptr(), ldG, wAc.data_ptr(), ldwA, wGc.data_ptr(), ldwG))
-
-    def build(i, b0, t0):
-        j = jobs[i]
-        return N.CovOuterSweepJob(j[0] + 4 * b0 * j[1], j[1], j[2], j[3], j[4] + 4 * b0 * nc * j[5],
-                                  *j[5:12], j[12] + 4 * t0 * j[13], j[13], j[14] + 4 * t0 * j[15], j[15])
-
-    return _run_sweep(build, workspace_bytes, call, len(jobs), nb, nc, nt, keep[0].device, max_workspace_bytes)
+    return _weighted(_sweep_jobs, N.CovSweepJob, terms, False, "kron_covariance_sweep_tiled", None,
+                     N.kron_cov_sweep_tiled_workspace_bytes, N.kron_cov_sweep_tiled, max_workspace_bytes)
 
 
 def kron_covariance_outer_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]],
@@ -938,8 +955,8 @@ def kron_covariance_outer_sweep(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Te
     (nt, nA), wG (nt, nG).  Returns (nt, nb, nc, nc) fp32 with kron_covariance_sweep's
     guarantees.
     """
-    return _sweep_outer(terms, "kron_covariance_outer_sweep", MAX_COV_CLASSES,
-                        N.kron_cov_outer_sweep_workspace_bytes, N.kron_cov_outer_sweep, max_workspace_bytes)
+    return _weighted(_sweep_jobs, N.CovOuterSweepJob, terms, True, "kron_covariance_outer_sweep", MAX_COV_CLASSES,
+                     N.kron_cov_outer_sweep_workspace_bytes, N.kron_cov_outer_sweep, max_workspace_bytes)
 
 
 def kron_covariance_outer_sweep_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]],
@@ -948,9 +965,8 @@ def kron_covariance_outer_sweep_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tens
     (nt, nb, nc, nc) fp32 result, nc not capped (kfac_kron_cov_outer_sweep_tiled).  The
     guarantees are kron_covariance_sweep's; against kron_covariance_outer_sweep (nc <= 32,
     another summation order) it agrees to fp32 rounding."""
-    return _sweep_outer(terms, "kron_covariance_outer_sweep_tiled", None,
-                        N.kron_cov_outer_sweep_tiled_workspace_bytes, N.kron_cov_outer_sweep_tiled,
-                        max_workspace_bytes)
+    return _weighted(_sweep_jobs, N.CovOuterSweepJob, terms, True, "kron_covariance_outer_sweep_tiled", None,
+                     N.kron_cov_outer_sweep_tiled_workspace_bytes, N.kron_cov_outer_sweep_tiled, max_workspace_bytes)
 
 
 def _sweep_calls(nc: int):
@@ -1050,10 +1066,7 @@ def log_det_sweep(eig_state, dampings) -> Tensor:
 # kfac_kron_cov_outer_full).  A damping grid costs no inversion and no eigendecomposition.
 def _full_shapes(VA: Tensor, VG: Tensor, W: Tensor):
     """(nA, nG, W as (nt, nA, nG)) after the shape checks, which need no device."""
-    for V, what in ((VA, "VA"), (VG, "VG")):
-        if V.dim() != 2 or V.shape[0] != V.shape[1]:
-            raise ValueError(f"{what} {tuple(V.shape)}: expected a square matrix of eigenvectors")
-    nA, nG = VA.shape[0], VG.shape[0]
+    nA, nG = _square(VA, "VA"), _square(VG, "VG")
     W = W.detach()
     if W.dim() == 2:
         W = W.unsqueeze(0)
@@ -1071,40 +1084,28 @@ def _full_weights(W: Tensor):
     return W, (W.stride(0) if nt > 1 else nA * nG)
 
 
-def _full_dense(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
-    """kron_covariance_full / kron_covariance_full_tiled: the terms parsed and checked (shapes
-    before anything touches the device), then `call` through _run_sweep; `max_classes` None:
-    no cap on nc."""
-    if not terms:
-        raise ValueError("no terms")
-    parsed = []
-    nb = nc = nt = None
-    for J, VA, VG, W in terms:
+def _full_jobs(terms, outer: bool, who: str, max_classes):
+    """(tensors to keep alive, per term (the job tuple up to ldG, [(W, ldW)]), nb, nc, nt) of
+    [(J_l, VA_l, VG_l, W_l)] or, outer, [(a_l, D_l, VA_l, VG_l, W_l)]."""
+    def shapes(term):
+        if outer:
+            a, D, VA, VG, W = term
+        else:
+            J, VA, VG, W = term
         nA, nG, W3 = _full_shapes(VA, VG, W)
-        J3, ld = _cov_rows(J, nA * nG)
-        if nb is None:
-            nb, nc, nt = J3.shape[0], J3.shape[1], W3.shape[0]
-        elif (J3.shape[0], J3.shape[1]) != (nb, nc):
-            raise ValueError("all terms need the same (nb, nc)")
-        if W3.shape[0] != nt or nt == 0:
-            raise ValueError("all weights need the same number nt >= 1 of matrices")
-        if max_classes is not None and nc > max_classes:
-            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
-        parsed.append((J3, ld, nA, nG, VA, VG, W3))
+        head = _outer_head(a, D, nA, nG, "VA", VA) if outer else _rows_head(J, nA, nG)
+        return head, (VA, VG, W3), (W3.shape[0],)
+
+    parsed, nb, nc, nt = _parse_terms(terms, shapes, who, max_classes, "matrices")
     keep, jobs = [], []
-    for J3, ld, nA, nG, VA, VG, W3 in parsed:
+    for head, (VA, VG, W3) in parsed:
         VAc, ldA = _sweep_basis(VA, "VA")
         VGc, ldG = _sweep_basis(VG, "VG")
-        N.require_device(J3, "J")
+        fields = head(keep)
         Wc, ldW = _full_weights(W3)
-        keep.extend([J3, VAc, VGc, Wc])
-        jobs.append((J3.data_ptr(), ld, nA, nG, VAc.data_ptr(), ldA, VGc.data_ptr(), ldG, Wc.data_ptr(), ldW))
-
-    def build(i, b0, t0):
-        j = jobs[i]
-        return N.CovFullJob(j[0] + 4 * b0 * nc * j[1], *j[1:8], j[8] + 4 * t0 * j[9], j[9])
-
-    return _run_sweep(build, workspace_bytes, call, len(jobs), nb, nc, nt, keep[0].device, max_workspace_bytes)
+        keep.extend([VAc, VGc, Wc])
+        jobs.append(((*fields, VAc.data_ptr(), ldA, VGc.data_ptr(), ldG), ((Wc.data_ptr(), ldW),)))
+    return keep, jobs, nb, nc, nt
 
 
 def kron_covariance_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]],
@@ -1119,8 +1120,8 @@ def kron_covariance_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]],
     that sample only, slice t has the bits of the call with W[t] alone.  Shapes are checked
     (ValueError) before anything touches the device.
     """
-    return _full_dense(terms, "kron_covariance_full", MAX_COV_CLASSES, N.kron_cov_full_workspace_bytes,
-                       N.kron_cov_full, max_workspace_bytes)
+    return _weighted(_full_jobs, N.CovFullJob, terms, False, "kron_covariance_full", MAX_COV_CLASSES,
+                     N.kron_cov_full_workspace_bytes, N.kron_cov_full, max_workspace_bytes)
 
 
 def kron_covariance_full_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]],
@@ -1131,57 +1132,8 @@ def kron_covariance_full_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Ten
     are kron_covariance_full's; with every weight 1 slice t has the bits of
     kron_covariance_tiled(lower=False) on the same rows; against kron_covariance_full
     (nc <= 32, another summation order) it agrees to fp32 rounding."""
-    return _full_dense(terms, "kron_covariance_full_tiled", None, N.kron_cov_full_tiled_workspace_bytes,
-                       N.kron_cov_full_tiled, max_workspace_bytes)
-
-
-def _full_outer(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
-    """kron_covariance_outer_full / kron_covariance_outer_full_tiled: as _full_dense."""
-    if not terms:
-        raise ValueError("no terms")
-    parsed = []
-    nb = nc = nt = None
-    for a, D, VA, VG, W in terms:
-        nA, nG, W3 = _full_shapes(VA, VG, W)
-        D3, ldD = _cov_rows(D, nG)
-        a2 = a.detach()
-        a2 = a2.reshape(1, -1) if a2.dim() == 1 else a2
-        if a2.dim() != 2:
-            raise ValueError(f"a {tuple(a2.shape)}: expected (nb, cols), a Linear layer's 2-D input")
-        cols = a2.shape[1]
-        if nA not in (cols, cols + 1) or cols == 0:
-            raise ValueError(f"a has {cols} columns, VA {tuple(VA.shape)} needs {nA} or {nA - 1}")
-        if nb is None:
-            nb, nc, nt = D3.shape[0], D3.shape[1], W3.shape[0]
-        elif (D3.shape[0], D3.shape[1]) != (nb, nc):
-            raise ValueError("all terms need the same (nb, nc)")
-        if a2.shape[0] != nb:
-            raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
-        if W3.shape[0] != nt or nt == 0:
-            raise ValueError("all weights need the same number nt >= 1 of matrices")
-        if max_classes is not None and nc > max_classes:
-            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
-        parsed.append((a2, cols, D3, ldD, nA, nG, VA, VG, W3))
-    keep, jobs = [], []
-    for a2, cols, D3, ldD, nA, nG, VA, VG, W3 in parsed:
-        VAc, ldA = _sweep_basis(VA, "VA")
-        VGc, ldG = _sweep_basis(VG, "VG")
-        if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols):
-            a2 = a2.contiguous()
-        lda = a2.stride(0) if nb > 1 else cols
-        for t, what in ((a2, "a"), (D3, "D")):
-            N.require_device(t, what)
-        Wc, ldW = _full_weights(W3)
-        keep.extend([a2, D3, VAc, VGc, Wc])
-        jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0,
-                     VAc.data_ptr(), ldA, VGc.data_ptr(), ldG, Wc.data_ptr(), ldW))
-
-    def build(i, b0, t0):
-        j = jobs[i]
-        return N.CovOuterFullJob(j[0] + 4 * b0 * j[1], j[1], j[2], j[3], j[4] + 4 * b0 * nc * j[5],
-                                 *j[5:12], j[12] + 4 * t0 * j[13], j[13])
-
-    return _run_sweep(build, workspace_bytes, call, len(jobs), nb, nc, nt, keep[0].device, max_workspace_bytes)
+    return _weighted(_full_jobs, N.CovFullJob, terms, False, "kron_covariance_full_tiled", None,
+                     N.kron_cov_full_tiled_workspace_bytes, N.kron_cov_full_tiled, max_workspace_bytes)
 
 
 def kron_covariance_outer_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
@@ -1194,8 +1146,8 @@ def kron_covariance_outer_full(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Ten
     them, W (nt, nA, nG) or (nA, nG).  Returns (nt, nb, nc, nc) fp32 with
     kron_covariance_full's guarantees.
     """
-    return _full_outer(terms, "kron_covariance_outer_full", MAX_COV_CLASSES,
-                       N.kron_cov_outer_full_workspace_bytes, N.kron_cov_outer_full, max_workspace_bytes)
+    return _weighted(_full_jobs, N.CovOuterFullJob, terms, True, "kron_covariance_outer_full", MAX_COV_CLASSES,
+                     N.kron_cov_outer_full_workspace_bytes, N.kron_cov_outer_full, max_workspace_bytes)
 
 
 def kron_covariance_outer_full_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]],
@@ -1204,9 +1156,8 @@ def kron_covariance_outer_full_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tenso
     (nt, nb, nc, nc) fp32 result, nc not capped (kfac_kron_cov_outer_full_tiled).  The
     guarantees are kron_covariance_full's; against kron_covariance_outer_full (nc <= 32,
     another summation order) it agrees to fp32 rounding."""
-    return _full_outer(terms, "kron_covariance_outer_full_tiled", None,
-                       N.kron_cov_outer_full_tiled_workspace_bytes, N.kron_cov_outer_full_tiled,
-                       max_workspace_bytes)
+    return _weighted(_full_jobs, N.CovOuterFullJob, terms, True, "kron_covariance_outer_full_tiled", None,
+                     N.kron_cov_outer_full_tiled_workspace_bytes, N.kron_cov_outer_full_tiled, max_workspace_bytes)
 
 
 def _full_calls(nc: int):
@@ -1372,30 +1323,30 @@ def _inf_operands(UA: Tensor, UG: Tensor, W: Tensor, F: Tensor):
                             W.data_ptr(), W.numel(), F.data_ptr(), ld(F))
 
 
+def _inf_jobs(terms, outer: bool, who: str, max_classes):
+    """_inf_dense_jobs (outer False) / _inf_outer_jobs (outer True)."""
+    def shapes(term):
+        if outer:
+            a, D, UA, UG, W, F = term
+        else:
+            J, UA, UG, W, F = term
+        nA, nG, _, _ = _inf_shapes(UA, UG, W, F)
+        return (_outer_head(a, D, nA, nG, "UA", UA) if outer else _rows_head(J, nA, nG)), (UA, UG, W, F), ()
+
+    parsed, nb, nc, _ = _parse_terms(terms, shapes, who, max_classes)
+    keep, jobs = [], []
+    for head, operands in parsed:
+        fields = head(keep)
+        held, tail = _inf_operands(*operands)
+        keep.extend(held)
+        jobs.append((*fields, *tail))
+    return keep, jobs, nb, nc
+
+
 def _inf_dense_jobs(terms, who, max_classes):
     """(tensors to keep alive, kfac_inf_cov_job tuples, nb, nc) of [(J_l, UA_l, UG_l, W_l, F_l)]
     (max_classes None: no cap)."""
-    if not terms:
-        raise ValueError("no terms")
-    parsed = []
-    nb = nc = None
-    for J, UA, UG, W, F in terms:
-        nA, nG, _, _ = _inf_shapes(UA, UG, W, F)
-        J3, ld = _cov_rows(J, nA * nG)
-        if nb is None:
-            nb, nc = J3.shape[0], J3.shape[1]
-        elif (J3.shape[0], J3.shape[1]) != (nb, nc):
-            raise ValueError("all terms need the same (nb, nc)")
-        if max_classes is not None and nc > max_classes:
-            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
-        parsed.append((J3, ld, nA, nG, UA, UG, W, F))
-    keep, jobs = [], []
-    for J3, ld, nA, nG, UA, UG, W, F in parsed:
-        N.require_device(J3, "J")
-        held, tail = _inf_operands(UA, UG, W, F)
-        keep.extend([J3, *held])
-        jobs.append((J3.data_ptr(), ld, nA, nG, *tail))
-    return keep, jobs, nb, nc
+    return _inf_jobs(terms, False, who, max_classes)
 
 
 def _inf_dense(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):
@@ -1448,40 +1399,7 @@ def kron_covariance_inf_tiled(terms: Sequence[Tuple[Tensor, Tensor, Tensor, Tens
 def _inf_outer_jobs(terms, who, max_classes):
     """(tensors to keep alive, kfac_inf_cov_outer_job tuples, nb, nc) of
     [(a_l, D_l, UA_l, UG_l, W_l, F_l)] (max_classes None: no cap)."""
-    if not terms:
-        raise ValueError("no terms")
-    parsed = []
-    nb = nc = None
-    for a, D, UA, UG, W, F in terms:
-        nA, nG, _, _ = _inf_shapes(UA, UG, W, F)
-        D3, ldD = _cov_rows(D, nG)
-        a2 = a.detach()
-        a2 = a2.reshape(1, -1) if a2.dim() == 1 else a2
-        if a2.dim() != 2:
-            raise ValueError(f"a {tuple(a2.shape)}: expected (nb, cols), a Linear layer's 2-D input")
-        cols = a2.shape[1]
-        if nA not in (cols, cols + 1) or cols == 0:
-            raise ValueError(f"a has {cols} columns, UA {tuple(UA.shape)} needs {nA} or {nA - 1}")
-        if nb is None:
-            nb, nc = D3.shape[0], D3.shape[1]
-        elif (D3.shape[0], D3.shape[1]) != (nb, nc):
-            raise ValueError("all terms need the same (nb, nc)")
-        if a2.shape[0] != nb:
-            raise ValueError(f"a has {a2.shape[0]} rows, D has {nb} samples")
-        if max_classes is not None and nc > max_classes:
-            raise ValueError(f"{who} handles at most {max_classes} outputs, got {nc}")
-        parsed.append((a2, cols, D3, ldD, nA, nG, UA, UG, W, F))
-    keep, jobs = [], []
-    for a2, cols, D3, ldD, nA, nG, UA, UG, W, F in parsed:
-        if a2.stride(1) != 1 or (nb > 1 and a2.stride(0) < cols):
-            a2 = a2.contiguous()
-        lda = a2.stride(0) if nb > 1 else cols
-        for t, what in ((a2, "a"), (D3, "D")):
-            N.require_device(t, what)
-        held, tail = _inf_operands(UA, UG, W, F)
-        keep.extend([a2, D3, *held])
-        jobs.append((a2.data_ptr(), lda, cols, int(nA == cols + 1), D3.data_ptr(), ldD, nG, 0, *tail))
-    return keep, jobs, nb, nc
+    return _inf_jobs(terms, True, who, max_classes)
 
 
 def _inf_outer(terms, who, max_classes, workspace_bytes, call, max_workspace_bytes):

@@ -3,17 +3,14 @@ variance.conv_jacobian_rows; the ctypes struct mirrors the header; and every arg
 of kfac_cov_conv_rows returns KFAC_EINVAL before any launch, alone and as the second job
 (dummy integers stand in for device pointers: nothing is dereferenced on the host)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import conv_rows_cases as R
-from conftest import ROOT
+from abi_layout import c_layout
 
-HEADER = os.path.join(ROOT, "include", "kfac_hip.h")
 FIELDS = ("x", "D", "ldD", "nG", "reserved", "M", "ldM")
 
 
@@ -63,14 +60,7 @@ def test_reference_is_conv_jacobian_rows(cid):
 
 def test_struct_layout_matches_header(tmp_path):
     from bnn_kfac_amd import _native as N
-    src = tmp_path / "sz.c"
-    offs = ", ".join(f"offsetof(kfac_cov_conv_rows_job, {f})" for f in FIELDS)
-    fmt = " ".join(["%zu"] * (1 + len(FIELDS)))
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\n'
-                   f'int main(void){{printf("{fmt}", sizeof(kfac_cov_conv_rows_job), {offs}); return 0;}}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    got = c_layout(tmp_path, "kfac_cov_conv_rows_job", FIELDS)
     assert [f for f, _ in N.CovConvRowsJob._fields_] == list(FIELDS)
     assert got == [ctypes.sizeof(N.CovConvRowsJob)] + [getattr(N.CovConvRowsJob, f).offset for f in FIELDS]
 

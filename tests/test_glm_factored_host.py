@@ -3,31 +3,20 @@
 variance.layer_io_jacobians against the dense output_jacobians rows in fp64.  No GPU
 calls."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 import torch
 import torch.nn as nn
 
-from conftest import ROOT
+from abi_layout import c_layout
 
-HEADER = os.path.join(ROOT, "include", "kfac_hip.h")
 FIELDS = ("a", "lda", "cols", "has_ones", "D", "ldD", "nG", "reserved", "K1", "ld1", "K2", "ld2",
           "lower1", "lower2")
 
 
 def test_cov_outer_struct_layout(tmp_path):
     from bnn_kfac_amd import _native as N
-    c = tmp_path / "sz.c"
-    offs = ", ".join(f"offsetof(kfac_cov_outer_job, {f})" for f in FIELDS)
-    fmt = " ".join(["%zu"] * (1 + len(FIELDS)))
-    c.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\n'
-                 f'int main(void){{printf("{fmt}", sizeof(kfac_cov_outer_job), {offs}); return 0;}}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-o", str(exe), str(c)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True,
-                                          check=True).stdout.split()]
+    got = c_layout(tmp_path, "kfac_cov_outer_job", FIELDS)
     assert [f for f, _ in N.CovOuterJob._fields_] == list(FIELDS)
     assert got == [ctypes.sizeof(N.CovOuterJob)] + [getattr(N.CovOuterJob, f).offset for f in FIELDS]
 

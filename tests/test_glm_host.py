@@ -2,16 +2,12 @@
 probit_predictive) and the C ABI of kfac_kron_cov (struct layout, argument validation
 before any launch, workspace query).  No GPU calls."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
-
-HEADER = os.path.join(ROOT, "include", "kfac_hip.h")
+from abi_layout import c_layout
 
 
 def _loop_reference(dW, db):
@@ -73,15 +69,7 @@ def test_probit_predictive_properties():
 
 def test_cov_struct_layout(tmp_path):
     from bnn_kfac_amd import _native as N
-    c = tmp_path / "sz.c"
-    c.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\n'
-                 'int main(void){printf("%zu %zu %zu %zu", sizeof(kfac_cov_job), '
-                 'offsetof(kfac_cov_job, K1), offsetof(kfac_cov_job, K2), '
-                 'offsetof(kfac_cov_job, lower2)); return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-o", str(exe), str(c)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True,
-                                          check=True).stdout.split()]
+    got = c_layout(tmp_path, "kfac_cov_job", ("K1", "K2", "lower2"))
     assert got == [ctypes.sizeof(N.CovJob), N.CovJob.K1.offset, N.CovJob.K2.offset,
                    N.CovJob.lower2.offset]
 

@@ -5,8 +5,6 @@ glm_inf_mc_cases, the recorded fp32 chain error behind the GPU tolerance, the la
 kfac_inf_draw_job / kfac_inf_draw_outer_job against the header, argument validation before any
 launch, and glm_predictive_mc's argument errors under an INF.  No GPU calls."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,9 +12,8 @@ import torch
 
 import glm_inf_cases as P
 import glm_inf_mc_cases as C
-from conftest import ROOT
+from abi_layout import c_layout
 
-HEADER = os.path.join(ROOT, "include", "kfac_hip.h")
 OUT, WS = 1 << 16, 1 << 17  # (pointers are never dereferenced: validation precedes any launch)
 POSTERIORS = [(6, 4, 3, 2, 3.0, 0.25), (5, 3, 2, 3, 1.0, 1.0), (4, 7, 4, 1, 0.5, 2.0), (3, 3, 3, 3, 10.0, 0.1)]
 
@@ -138,14 +135,7 @@ def test_inf_draw_struct_layout_matches_header(tmp_path, cname, pyname, rows):
     from bnn_kfac_amd import _native as N
     S = getattr(N, pyname)
     fields = ("rows",) + TAIL
-    c = tmp_path / "sz.c"
-    offs = ", ".join(f"offsetof({cname}, {f})" for f in fields)
-    fmt = " ".join(["%zu"] * (1 + len(fields)))
-    c.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\n'
-                 f'int main(void){{printf("{fmt}", sizeof({cname}), {offs}); return 0;}}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-o", str(exe), str(c)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    got = c_layout(tmp_path, cname, fields)
     assert [f for f, _ in S._fields_] == list(fields)
     assert got == [ctypes.sizeof(S)] + [getattr(S, f).offset for f in fields]
     assert S.rows.offset == 0 and S.C.offset == ctypes.sizeof(getattr(N, rows))

@@ -4,17 +4,14 @@ kfac_glm_draws_outer / kfac_softmax_mc before any launch, the workspace queries,
 reference formulas of glm_mc_cases against each other, and the int64 bound of every integer
 case the GPU test compares bit for bit.  No GPU calls."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import glm_mc_cases as C
-from conftest import ROOT
+from abi_layout import c_layout
 
-HEADER = os.path.join(ROOT, "include", "kfac_hip.h")
 OUT, WS = 1 << 16, 1 << 17  # (pointers are never dereferenced: validation precedes any launch)
 
 
@@ -29,16 +26,8 @@ def _outer_job(N, cols=4, has_ones=1, nG=3):
 
 def test_draw_struct_layout(tmp_path):
     from bnn_kfac_amd import _native as N
-    c = tmp_path / "sz.c"
-    c.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\n'
-                 'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu", sizeof(kfac_draw_job), '
-                 'offsetof(kfac_draw_job, rows), offsetof(kfac_draw_job, Z), offsetof(kfac_draw_job, ldZ), '
-                 'sizeof(kfac_draw_outer_job), offsetof(kfac_draw_outer_job, rows), '
-                 'offsetof(kfac_draw_outer_job, Z), offsetof(kfac_draw_outer_job, ldZ)); return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-o", str(exe), str(c)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True,
-                                          check=True).stdout.split()]
+    got = (c_layout(tmp_path, "kfac_draw_job", ("rows", "Z", "ldZ")) +
+           c_layout(tmp_path, "kfac_draw_outer_job", ("rows", "Z", "ldZ")))
     assert got == [ctypes.sizeof(N.DrawJob), N.DrawJob.rows.offset, N.DrawJob.Z.offset, N.DrawJob.ldZ.offset,
                    ctypes.sizeof(N.DrawOuterJob), N.DrawOuterJob.rows.offset, N.DrawOuterJob.Z.offset,
                    N.DrawOuterJob.ldZ.offset]

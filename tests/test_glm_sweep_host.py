@@ -3,17 +3,14 @@ kfac_kron_cov_outer_sweep (struct layouts, argument validation before any launch
 workspace queries), variance.damping_weights / log_det_sweep against numpy, and the
 lifetime of KFAC.eigh's cache.  No GPU calls."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
-from conftest import ROOT
+from abi_layout import c_layout
 
-HEADER = os.path.join(ROOT, "include", "kfac_hip.h")
 DENSE_FIELDS = ("J", "ldJ", "nA", "nG", "VA", "ldA", "VG", "ldG", "wA", "ldwA", "wG", "ldwG")
 OUTER_FIELDS = ("a", "lda", "cols", "has_ones", "D", "ldD", "nG", "reserved", "VA", "ldA", "VG", "ldG",
                 "wA", "ldwA", "wG", "ldwG")
@@ -25,15 +22,7 @@ GRID = [(0.04, 200.0), (1.0, 200.0), (1e-4, 1.0), (1e-6, 1e4)]
 def test_sweep_struct_layout(tmp_path, cname, pyname, fields):
     from bnn_kfac_amd import _native as N
     S = getattr(N, pyname)
-    c = tmp_path / "sz.c"
-    offs = ", ".join(f"offsetof({cname}, {f})" for f in fields)
-    fmt = " ".join(["%zu"] * (1 + len(fields)))
-    c.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\n'
-                 f'int main(void){{printf("{fmt}", sizeof({cname}), {offs}); return 0;}}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-o", str(exe), str(c)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True,
-                                          check=True).stdout.split()]
+    got = c_layout(tmp_path, cname, fields)
     assert [f for f, _ in S._fields_] == list(fields)
     assert got == [ctypes.sizeof(S)] + [getattr(S, f).offset for f in fields]
 

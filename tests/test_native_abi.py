@@ -3,13 +3,13 @@ ctypes structs mirror the C structs byte for byte (no GPU calls)."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_layout import HEADER, c_layout
 from conftest import ROOT
 
-HEADER = os.path.join(ROOT, "include", "kfac_hip.h")
+from bnn_kfac_amd import _native as N
 
 
 def declared_symbols():
@@ -41,13 +41,24 @@ def test_struct_layout_matches_header(tmp_path, name):
     pyname = {"kfac_operand": "Operand", "kfac_factor_job": "FactorJob",
               "kfac_invert_job": "InvertJob", "kfac_eig_job": "EigJob",
               "kfac_quad_job": "QuadJob", "kfac_tri_job": "TriJob"}[name]
-    c = tmp_path / "sz.c"
-    c.write_text(f'#include <stdio.h>\n#include "{HEADER}"\n'
-                 f'int main(void){{printf("%zu", sizeof({name})); return 0;}}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-o", str(exe), str(c)], check=True)
-    size = int(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
+    (size,) = c_layout(tmp_path, name)
     assert size == ctypes.sizeof(getattr(N, pyname))
+
+
+@pytest.mark.parametrize("name", sorted(N.STRUCTS))
+def test_every_struct_field_matches_header(tmp_path, name):
+    """Size and the offset of EVERY field of every ctypes.Structure of the binding."""
+    S = N.STRUCTS[name]
+    fields = [f for f, _ in S._fields_]
+    assert c_layout(tmp_path, name, fields) == [ctypes.sizeof(S)] + [getattr(S, f).offset for f in fields]
+
+
+def test_structs_lists_every_structure():
+    mirrors = {v for v in vars(N).values() if isinstance(v, type) and issubclass(v, ctypes.Structure)
+               and v.__module__ == N.__name__}
+    assert mirrors == set(N.STRUCTS.values()) and len(mirrors) == len(N.STRUCTS)
+    header = open(HEADER).read()
+    assert sorted(N.STRUCTS) == sorted(re.findall(r"^\} (kfac_\w+);", header, flags=re.M))
 
 
 def test_workspace_queries_need_no_gpu():
@@ -71,14 +82,7 @@ def test_workspace_queries_need_no_gpu():
 
 def test_sample_struct_layout(tmp_path):
     from bnn_kfac_amd import _native as N
-    c = tmp_path / "sz.c"
-    c.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\n'
-                 'int main(void){printf("%zu %zu %zu", sizeof(kfac_sample_job), '
-                 'offsetof(kfac_sample_job, W), offsetof(kfac_sample_job, wcols)); return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-o", str(exe), str(c)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True,
-                                          check=True).stdout.split()]
+    got = c_layout(tmp_path, "kfac_sample_job", ("W", "wcols"))
     assert got == [ctypes.sizeof(N.SampleJob), N.SampleJob.W.offset, N.SampleJob.wcols.offset]
     # argument validation happens before any launch
     assert N.lib().kfac_sample(N.as_array(N.SampleJob, [N.SampleJob()]), 1, 0, None, 0,

@@ -2,14 +2,11 @@
 header, the workspace queries, and argument validation before any launch.  No GPU calls
 (pointers are never dereferenced on the host)."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
-from conftest import ROOT
+from abi_layout import c_layout
 
-HEADER = os.path.join(ROOT, "include", "kfac_hip.h")
 DENSE_FIELDS = ("J", "ldJ", "nA", "nG", "UA", "ldA", "ra", "UG", "ldG", "rg", "W", "ldW", "F", "ldF")
 OUTER_FIELDS = ("a", "lda", "cols", "has_ones", "D", "ldD", "nG", "reserved", "UA", "ldA", "ra", "UG", "ldG",
                 "rg", "W", "ldW", "F", "ldF")
@@ -20,15 +17,7 @@ OUTER_FIELDS = ("a", "lda", "cols", "has_ones", "D", "ldD", "nG", "reserved", "U
 def test_inf_struct_layout_matches_header(tmp_path, cname, pyname, fields):
     from bnn_kfac_amd import _native as N
     S = getattr(N, pyname)
-    c = tmp_path / "sz.c"
-    offs = ", ".join(f"offsetof({cname}, {f})" for f in fields)
-    fmt = " ".join(["%zu"] * (1 + len(fields)))
-    c.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\n'
-                 f'int main(void){{printf("{fmt}", sizeof({cname}), {offs}); return 0;}}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-o", str(exe), str(c)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True,
-                                          check=True).stdout.split()]
+    got = c_layout(tmp_path, cname, fields)
     assert [f for f, _ in S._fields_] == list(fields)
     assert got == [ctypes.sizeof(S)] + [getattr(S, f).offset for f in fields]
     # the outer job starts like kfac_cov_outer_sweep_job: its first eight fields
